@@ -8,12 +8,11 @@ scaling: every rank runs `--batch` images per step); the packed weights are broa
 over RCCL before timing.  A "step" = one pass of the whole hot path over one batch already
 resident in HBM: input quantisation + space-to-depth, all 54 layers, logits copy.  Consecutive
 steps are independent batches: by default four are in flight (`--inflight`, step i on HIP stream
-i % 4 with its own workspace; the HIP runtime's hardware-queue count is raised so that each of these streams has
-its own queue, see GPU_MAX_HW_QUEUES below) so that the latency-bound small layers of one batch overlap with
+i % 4 with its own workspace) so that the latency-bound small layers of one batch overlap with
 another batch's kernels; all K timed steps complete inside the timed region, and the
 one-batch-at-a-time rate is reported beside it (`images_per_s_one_batch_at_a_time`).
 
-`--gpus N` without a torchrun environment re-executes itself under `python -m torch.distributed.run` with N ranks on
+`--gpus N` without a torchrun environment runs itself as a child process under `python -m torch.distributed.run` with N ranks on
 127.0.0.1 (one per GPU); under torchrun it asserts WORLD_SIZE == N.  Every rank pins LOCAL_RANK -> GPU and fails
 loudly if that GPU does not exist.  `--spawn-check` runs only that launch / pin / broadcast logic (gloo on CPU when
 there is no GPU) -- tests/test_dist_cpu.py drives it through this file.
@@ -30,11 +29,6 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# The HIP runtime multiplexes streams onto 4 hardware queues by default, one of them held by the null stream: a fourth
-# in-flight stream would share a queue and serialise behind another batch (measured: 62.8 k img/s with 4 streams on the
-# default against 74.5 k with >= 5 queues, profiles/r02_inflight_hwqueues.txt).  Read by the runtime at initialisation,
-# so it is set before torch loads it; a deployment that keeps several batches in flight sets the same variable.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 
 def layer_ops(plan):
@@ -66,6 +60,26 @@ def launch_groups(cls, launches, kinds):
         per = next(p for p in range(1, len(seq) + 1) if len(seq) % p == 0 and seq == seq[:p] * (len(seq) // p))
         out.append(("+".join(seq[:per]) if per == len(seq) else f"{len(seq) // per} x ({'+'.join(seq[:per])})", g))
     return out
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each array as out_dir/<name>.npy in float32.  Past DUMP_CAP_BYTES in all, an array is replaced by a fixed sample of its
+    flattened elements (seed 0, sorted indices), so that two runs of the same arguments still write the same files."""
+    os.makedirs(out_dir, exist_ok=True)
+    room = DUMP_CAP_BYTES // 4 // max(1, len(arrays))
+    files = {}
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        shape = list(a.shape)
+        if a.size > room:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, room, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        files[name] = dict(shape=shape, written=list(a.shape), dtype="float32")
+    return dict(dir=out_dir, files=files)
 
 
 def spawn_check(args):
@@ -170,11 +184,16 @@ def main():
     ap.add_argument("--split", type=int, default=1, help="run every batch as this many sub-batches on concurrent streams (Runner.run_split)")
     ap.add_argument("--spawn-check", action="store_true", help="only launch N ranks, pin, broadcast a small network, report")
     ap.add_argument("--master-port", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region of record, write the logits its last step returned (rank 0) as DIR/logits.npy, float32; "
+                         "inputs and weights are seeded, so the same arguments give the same arrays")
     args = ap.parse_args()
 
     # ---- N ranks: re-exec under torchrun when started bare -------------------------------------------------------
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         import socket
         port = args.master_port
@@ -182,7 +201,8 @@ def main():
             sk = socket.socket(); sk.bind(("127.0.0.1", 0)); port = sk.getsockname()[1]; sk.close()
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-        os.execv(sys.executable, cmd)
+        import subprocess
+        return subprocess.call(cmd)
     env_world = int(os.environ.get("WORLD_SIZE", "1"))
     if env_world != args.gpus:
         sys.exit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={env_world}: launch with --nproc-per-node {args.gpus} "
@@ -234,6 +254,7 @@ def main():
     n_buf = (n_buf + n_inflight - 1) // n_inflight * n_inflight
     fl_runners = [network.Runner(None, net) for _ in range(n_inflight)] if n_inflight > 1 else []
     step_no = [0]
+    last_runner = [None]  # the Runner whose logits tensor holds what the latest step returned
     graphs = {}
     serial = [False]      # True: one batch at a time on the default stream (reported next to the pipelined figure)
 
@@ -254,6 +275,7 @@ def main():
         if n_inflight > 1 and not serial[0]:
             i = step_no[0] % n_inflight
             step_no[0] += 1
+            last_runner[0] = fl_runners[i]
             if feeder[0] is not None:
                 feeder[0].submit(i, lambda rn: rn.run_batch(x, concurrency=1))
                 return
@@ -278,8 +300,10 @@ def main():
             if key not in graphs:
                 r = network.Runner(None, net)
                 graphs[key] = (r, r.capture(x, split=args.split, concurrency=0))
+            last_runner[0] = graphs[key][0]
             graphs[key][1]()
         else:
+            last_runner[0] = runner
             one(runner, x)
 
     input_sets = {}
@@ -317,6 +341,7 @@ def main():
                 if feeder[0] is not None:
                     feeder[0].drain()
                 torch.cuda.synchronize(device)
+        step_no[0] = 0                         # the spin-up ran a time-bounded number of steps: W + K always start the rotation afresh
         for _ in range(warmup):
             step(xs)
         barrier()
@@ -345,6 +370,9 @@ def main():
                          "(idle power state, engine clock still ramping: tools/clock_sample.py)")
     dt, x = timed(args.batch, args.steps, args.warmup)
     ms_per_step = dt / args.steps * 1e3
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, dict(logits=last_runner[0]._logits.cpu().numpy()))
     value = world * args.batch * args.steps / dt
     # the same region again (device warm: no further spin-up), W warm-up steps in front of each: how far the figure of record moves
     rep_vals = [value]
@@ -639,6 +667,8 @@ def main():
                              bytes_per_image=sum(r["bytes"] for r in lo)),
                     per_layer_class=per_class, per_layer_class_one_batch=per_class_one_batch, images_per_s_by_batch=sweep,
                     images_per_s_one_batch_at_a_time=serial_value, latency_batch1=lat, pipeline_evidence=pipe)
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         print(json.dumps(line))
     if world > 1:
         dist.barrier()
@@ -646,4 +676,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

@@ -23,6 +23,9 @@ What it writes (all data: inputs + expected outputs, never reference source text
   ref_caq.npz              outputs of the reference's calibrator functions QuantizeForShift / QuantizeChannel
   ref_caq_squeezenet.npz   Q vectors of the reference's own calibration pass (feature_hook + QuantizeChannel) over its own
                            SqueezeNet 1.1 forward at 1x3x227x227 with seeded parameters (BASELINE configs[0])
+  ref_oracle_vs_ref.npz    seeded fuzz inputs and the reference's own outputs for them: Get_real, filter_trans, feature_trans
+                           (oracle/_ref/libtf2ref_resnet50.so), MUL on every (feature, code) pair and DotProduct
+                           (oracle/_ref/libtf2ref_pe.so, pe.cl compiled as C); tests/test_oracle_vs_ref.py
   ref_ssd.npz              outputs of the reference's SSD PriorBox / decode / nms (+ the L2Norm formula)
                            (TransForm_Kit/Quantization/debug/...Batch-2.py: Conv2dInt8, BN, FC),
                            AST-extracted and executed here.
@@ -501,6 +504,52 @@ def gen_ssd():
     np.savez_compressed(os.path.join(OUT, "ref_ssd.npz"), **out)
 
 
+def gen_oracle_vs_ref():
+    """The reference's compiled host functions and PE arithmetic on seeded fuzz inputs (inputs stored beside the outputs)."""
+    L = C.CDLL(os.path.join(REFOUT, "libtf2ref_resnet50.so"))
+    L._Z8Get_realfc.restype = C.c_char
+    L._Z8Get_realfc.argtypes = [C.c_float, C.c_char]
+    out = {}
+    rng = np.random.default_rng(3)
+    vals = np.concatenate([rng.normal(0, 0.3, 3000), np.ldexp(rng.choice([-1.0, 1.0], 3000) * rng.uniform(0.985, 1.015, 3000),
+                                                                -rng.integers(0, 17, 3000))]).astype(np.float32)
+    exps = rng.integers(-5, 40, vals.size).astype(np.int8)
+    out["get_real_w"], out["get_real_e"] = vals, exps
+    out["get_real_out"] = np.asarray([L._Z8Get_realfc(C.c_float(float(v)), C.c_char(int(e) & 0xff))[0] for v, e in zip(vals, exps)], np.uint8)
+    rng = np.random.default_rng(4)
+    planes = rng.integers(0, 256, (50, 49)).astype(np.uint8)
+    ft = np.zeros((50, 81), np.uint8)
+    for i in range(50):
+        L._Z12filter_transPcS_(planes[i].ctypes.data_as(C.c_void_p), ft[i].ctypes.data_as(C.c_void_p))
+    out["filter_trans_in"], out["filter_trans_out"] = planes, ft
+    rng = np.random.default_rng(5)
+    plane = rng.normal(0, 60, 224 * 224).astype(np.float32)
+    fo = np.zeros(9 * 115 * 115 + 2048, np.float32)
+    L._Z13feature_transPfS_(plane.ctypes.data_as(C.c_void_p), fo.ctypes.data_as(C.c_void_p))
+    out["feature_trans_in"] = plane
+    out["feature_trans_out"] = np.ascontiguousarray(fo[:9 * 115 * 115].reshape(9, 115, 115)[:, :114, :114])
+    PE = C.CDLL(os.path.join(REFOUT, "libtf2ref_pe.so"))
+    PE.tf2ref_pe_mul.restype = C.c_int
+    PE.tf2ref_pe_mul.argtypes = [C.c_int, C.c_int]
+    PE.tf2ref_pe_dot.restype = C.c_int
+    PE.tf2ref_pe_dot.argtypes = [C.c_void_p, C.c_void_p]
+    out["pe_mul"] = np.asarray([[PE.tf2ref_pe_mul(x, code) for code in range(256)] for x in range(-128, 128)], np.int32)
+    out["pe_c_vector"] = np.asarray(PE.tf2ref_pe_c_vector(), np.int32)
+    rng = np.random.default_rng(11)
+    xs, cs = [], []
+    for trial in range(3000):
+        x = rng.integers(-128, 128, 16).astype(np.int8)
+        if trial % 3 == 0:
+            codes = (rng.integers(24, 32, 16) | (rng.integers(0, 2, 16) << 7)).astype(np.uint8)        # long shifts: the sum wraps
+            x = rng.choice(np.array([-128, -127, 127], np.int8), 16)
+        else:
+            codes = rng.integers(0, 256, 16).astype(np.uint8)
+        xs.append(x); cs.append(codes)
+    out["pe_dot_x"], out["pe_dot_codes"] = np.stack(xs), np.stack(cs)
+    out["pe_dot_out"] = np.asarray([PE.tf2ref_pe_dot(x.ctypes.data, c.ctypes.data) for x, c in zip(out["pe_dot_x"], out["pe_dot_codes"])], np.int32)
+    np.savez_compressed(os.path.join(OUT, "ref_oracle_vs_ref.npz"), **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     if not os.path.isdir(REF):
@@ -512,4 +561,5 @@ if __name__ == "__main__":
     gen_caq()
     gen_caq_squeezenet()
     gen_ssd()
+    gen_oracle_vs_ref()
     print("golden fixtures written to", OUT)

@@ -63,3 +63,46 @@ def test_bench_other_network_same_line():
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert "SqueezeNet" in d["metric"] and "227x227" in d["config"]["workload"] and d["value"] > 0
     assert d["roofline"]["frac"] > 0 and d["roofline"]["one_batch"]["one_at_a_time"]["frac"] > 0 and d["cpu_baseline"]["parity_with_gpu_logits"] is True
+
+
+def test_dump_outputs_caps_by_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.dump_outputs: float32 .npy per array; past the cap a seeded sample of the flattened elements, the same on every call."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    small = np.arange(-6, 6, dtype=np.int8).reshape(3, 4)
+    d = bench.dump_outputs(str(tmp_path / "a"), dict(logits=small))
+    got = np.load(tmp_path / "a" / "logits.npy")
+    assert got.dtype == np.float32 and (got == small).all() and d["files"]["logits"]["shape"] == [3, 4]
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 4 * 100)
+    big = np.random.default_rng(1).integers(-128, 128, (40, 50)).astype(np.int8)
+    bench.dump_outputs(str(tmp_path / "b"), dict(logits=big))
+    bench.dump_outputs(str(tmp_path / "c"), dict(logits=big))
+    b, c = np.load(tmp_path / "b" / "logits.npy"), np.load(tmp_path / "c" / "logits.npy")
+    assert b.shape == (100,) and b.dtype == np.float32 and (b == c).all()
+    assert np.isin(b, big.astype(np.float32)).all()
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """--dump-outputs: the logits of the last timed step, whose input is the seeded batch (W + K - 1) mod n_buf of the rotation;
+    its first images equal the oracle's logits of the same input."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    from oracle import netref
+    from tf2_amd import synth
+    steps, warmup, batch = 5, 2, 8
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--batch", str(batch),
+                          "--no-cpu", "--extra-batches", "", "--repeats", "1", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, cwd=ROOT, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+    assert d["steps"] == steps and d["ms_per_step"] > 0 and d["dumped_outputs"]["files"]["logits"]["shape"] == [batch, 1000]
+    got = np.load(tmp_path / "logits.npy")
+    assert got.dtype == np.float32 and got.shape == (batch, 1000)
+    tables, qv, seed_m, _, _ = synth.bench_network("resnet50")
+    k = (warmup + steps - 1) % d["config"]["input_buffers_rotated"]
+    x = synth.synth_images(tables, batch, seed=100 + 17 * k)
+    ref = netref.RefNet(tables, qv, synth.synth_model(tables, qv, seed=seed_m))
+    want = ref.logits(ref.run(x[:2]))
+    np.testing.assert_array_equal(got[:2], want.astype(np.float32))

@@ -182,12 +182,11 @@ def test_resnet50_batch_sizes_and_tile_choices(r50, monkeypatch, conc):
 @pytest.mark.parametrize("graph", [0, 1])
 def test_four_batches_in_flight_as_bench_times_them(r50, graph):
     """The configuration bench.py's headline is timed in, checked as executed: ONE Net, four Runners (own workspaces) on four
-    HIP streams (GPU_MAX_HW_QUEUES=8 from conftest), the library's stream-history heuristic left on auto, eight different
+    HIP streams, the library's stream-history heuristic left on auto, eight different
     batch-32 inputs issued round-robin for 16 steps with no synchronisation in between -- launched, and replayed from captured
     HIP graphs.  Every logits row of the last four steps: three rows per batch against the oracle, all 32 against a serial
     run_batch of the same input (feature_writer.cl:88-151 is the output contract of each step)."""
     torch = _torch()
-    assert os.environ.get("GPU_MAX_HW_QUEUES") == "8"
     rig = Rig(*r50, 0)
     n_fl, n_in, n_steps = 4, 8, 32
     xs = [synth.synth_images(rig.t, 32, 300 + i) for i in range(n_in)]

@@ -9,21 +9,12 @@ from __future__ import annotations
 import ctypes as C
 import os
 import re
-import sys
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# One hardware queue per in-flight stream: the HIP runtime multiplexes streams onto 4 hardware queues by default (one of them the
-# null stream's), so a fourth in-flight batch would queue behind another (-15 %, profiles/r02_inflight_hwqueues.txt).  The runtime
-# reads the variable when it initialises, i.e. it only takes effect if tf2_amd is imported before the first HIP call of the
-# process; a deployment that embeds the C library directly exports it itself (INTEGRATION.md "Deployment preconditions").
-if "GPU_MAX_HW_QUEUES" not in os.environ:
-    os.environ["GPU_MAX_HW_QUEUES"] = "8"
-    _torch_mod = sys.modules.get("torch")
-    if _torch_mod is not None and getattr(getattr(_torch_mod, "cuda", None), "is_initialized", lambda: False)():
-        import warnings
-        warnings.warn("tf2_amd: HIP was initialised before tf2_amd was imported, GPU_MAX_HW_QUEUES=8 cannot take effect any more: a fourth "
-                      "batch in flight will share a hardware queue (export GPU_MAX_HW_QUEUES=8 before starting the process)", RuntimeWarning)
+# The library leaves the HIP runtime's hardware-queue count to the process environment: streams of one process share its
+# queues, so batches in flight on several streams still run, with less overlap when there are fewer queues than streams
+# (INTEGRATION.md "Deployment preconditions").
 # TF2_AMD_LIB: another build of the same sources (the tools' -DTF2_PROBES / -DTF2_CHECK_DMA libraries); never a fallback, and refused
 # unless the process also sets TF2_AMD_TOOL_LIB=1 (lib() below: a tool build can leave work out of a step)
 LIB_PATH = os.environ.get("TF2_AMD_LIB") or os.path.join(_HERE, "libtf2amd.so")

@@ -2,7 +2,6 @@
 """Throughput of the other BASELINE.json configurations (synthetic weights / Q / images, one MI355X): images/s one batch at a
 time and with four batches in flight.  bench.py measures the headline network; this is the breadth table of DESIGN.md section 5."""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np

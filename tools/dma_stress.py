@@ -21,7 +21,6 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 DMA_KERNELS = ("conv_bband_kernel", "conv_bfirst_kernel", "conv_bneck_kernel", "conv_c3_kernel", "conv_c3_w9_kernel", "fc_partial_kernel", "fc4_partial_kernel", "conv_fire_kernel", "conv_first_kernel",
                "conv_pwk_kernel", "conv_pwk_pair_kernel")      # (round 6: the persistent pointwise kernel's hand-written DMA waits)

@@ -8,7 +8,6 @@ import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from tf2_amd._lib import set_opts  # noqa: E402
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 os.environ["TF2_AMD_LIB"] = os.path.join(ROOT, "tf2_amd", "libtf2amd_probe.so"); os.environ["TF2_AMD_TOOL_LIB"] = "1"     # (built on demand: make -C tf2_amd/csrc probe)
 import numpy as np
 import torch

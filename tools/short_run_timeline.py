@@ -5,7 +5,6 @@ the host starts enqueuing.  usage: short_run_timeline.py [steps] [inflight] [war
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np
 import torch
 from tf2_amd import config as cfg, network, synth, streams
