@@ -1017,7 +1017,12 @@ const LaunchPlan* Net::launch_plan(int batch, const WorkPlan* wp, void* ws, bool
     const int bn_R = pl->fuse_next > 0 ? std::min(bn_TN / L.W, L.H) : 1;
     // (128-channel pairs: 42.6 against 46.8 us at batch 64 one batch at a time, but 0.62 against 0.51 us per further image --
     //  with batches in flight the two separate launches win)
-    const bool fuse_now = pl->fuse_next > 0 && (long)batch * ((L.H + bn_R - 1) / bn_R) >= opts.bneck_min_blocks &&
+    // conv_bneck.hip's phase 2 addresses the expand's output (the tensor its conv writes) and its residual as kernel-argument base + ONE
+    // 32-bit byte offset (pixel * Cp + channel offset; the input and the intermediate map use 64-bit addresses): a pair whose expand
+    // tensors reach 2^32 bytes runs as the two separate launches (conv_pwk_eligible has the same guard)
+    auto below_4g = [&](int tid) { return tid < 0 || (unsigned long long)T(tid).bytes < (1ull << 32); };
+    const bool bneck_fits = pl->fuse_next > 0 && below_4g(wp->exec[pl->fuse_next].conv_tensor) && below_4g(wp->exec[pl->fuse_next].res_tensor);
+    const bool fuse_now = pl->fuse_next > 0 && bneck_fits && (long)batch * ((L.H + bn_R - 1) / bn_R) >= opts.bneck_min_blocks &&
                           !(concurrent && pl->TM == 128 && opts.bneck_min_blocks > 1);
     if (!make_conv(l, st, !fuse_now)) return nullptr;     // the fused launch needs the pair's own (one m-tile) entries
     if (!fuse_now && (opts.fc_mode || pack_layer(l)->fc4) && fc_at(l, batch) && wp->scratch_bytes) {

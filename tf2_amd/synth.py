@@ -166,3 +166,205 @@ def bench_network(name: str):
                       "ssd300": (cfg.ssd300_tables, "SSD300-VGG", 3)}[name]
     t = mk()
     return t, synth_q_values(t, seed, spread=1), seed, disp, "TF2 table program built by tf2_amd.config, synthetic per-channel Q values and seeded INQ weights"
+
+
+# ---- extreme-regime models: parameters chosen so that the edges of the integer arithmetic are reached ----------------------------------
+EXTREME_REGIMES = ("wrap", "saturate", "spread", "shift22", "shift23", "expand32")
+
+
+def _stream_offsets(plan):
+    """Per table row: offsets {w, bias, mean, var, sf, gamma, beta} (None where absent) into the LoadModel stream."""
+    pos, offs = 0, []
+    for L in plan:
+        o = dict(w=None, bias=None, mean=None, var=None, sf=None, gamma=None, beta=None)
+        if not L.ipool:
+            o["w"] = pos; pos += L.N * L.model_C * L.model_k * L.model_k
+        elif L.ipool == 2:
+            pos += L.N
+        if L.bias_en:
+            o["bias"] = pos; pos += L.N
+        if L.bn_en:
+            o["mean"] = pos; o["var"] = pos + L.N; o["sf"] = pos + 2 * L.N; o["gamma"] = pos + 2 * L.N + 1; o["beta"] = pos + 3 * L.N + 1
+            pos += 4 * L.N + 1
+        offs.append(o)
+    return offs
+
+
+def _q_layout(tables, plan):
+    """File-order Q positions: {row index: slice of its N values} (the image row's values come first)."""
+    pos, out = 3, {}
+    for L in plan:
+        if L.ipool == 1:
+            continue
+        out[L.index] = slice(pos, pos + L.N)
+        pos += L.N
+    return out, pos
+
+
+def synth_extreme(tables: cfg.NetTables, seed: int, regime: str, rows=None, q_spread: int = 1):
+    """(q_values, model_stream) in the same formats as synth_q_values / synth_model, with the rows `rows` (default: every conv row
+    but the image row, which takes the treatment only when named) pushed to an arithmetic edge; everything else is synth_q_values(
+    spread=q_spread) and synth_model.  Regimes (the numbers are in the oracle's terms: a filter code's shift is expand - level with
+    expand = 15 - Q_in[c] + Q_out[n] in file Q values, level = -log2|w|, tf2_oracle.c tf2o_encode_filters):
+
+    wrap      Q_out 10 above the row's input Q and dense filters of magnitude 1 .. 1/8: shifts of 22 .. 25, so that
+              bias + (sum << lo) wraps in Z/2^32 on a large share of the outputs.  The epilogue form is decided per LAYER (the pack-time
+              proof covers all its channels): a targeted layer with an even table index gets BN scales of 2^-9 .. 2^-7 on every channel
+              (|alpha| < 2^19: the SEMI form), an odd one scales of 1 .. 4 (only the generic six-instruction form may take them).  A
+              targeted row that reads a boosted tensor drops its Q 8 below it instead (scales 1 .. 4), so that chains alternate.
+    saturate  BN scales 32 .. 128 times the one that keeps activations in range and shifts of up to +-128 output units: most outputs clip at
+              127 / -128 (-128 where the row has no ReLU); every eighth row is all-zero with beta just below 2^31 - 2^14 or above
+              -2^31 (the generic form's x + 2^14 saturates); rows without ReLU in front of a residual get betas far below -128 (the
+              single-clamp form of a post-ReLU residual).
+    spread    per-channel output Q from 0 to 13 on the rows' producers and filters over all 15 levels: 3 to 5 exponent windows per row.
+              Row 0 of a layer has one non-zero tap, row 1 none; when a layer has more than 64 rows, rows 64 .. 127 use the low levels
+              only (rows with fewer windows than their layer); the layer after a targeted one keeps levels 0 .. 7 (two windows: the
+              dual form).
+    shift22 / shift23   Q_out = min(Q_in) + 7 / + 8 with dense filters that include magnitude 1: the layer's largest shift is exactly
+              22 / 23 (conv_shift.hip's mad_i32_i24 / 32-bit multiply boundary).
+    expand32  the producer of a targeted row writes its channel 0 with Q -3 and the row's Q_out is 14: expand = 32 on that channel, so
+              a magnitude-1 weight encodes as 0x20, which shifts by 0 (pe.cl's & 0x1f); the other channels' shifts reach 24 .. 27.
+    """
+    assert regime in EXTREME_REGIMES, regime
+    rng = np.random.default_rng(7000 + seed)
+    plan = cfg.build_plan(tables)
+    q = synth_q_values(tables, seed, spread=q_spread).astype(np.int32)
+    model = synth_model(tables, q, seed).astype(np.float32)
+    qpos, _ = _q_layout(tables, plan)
+    conv_rows = [L.index for L in plan if not L.ipool and L.src != -1]
+    targets = set(conv_rows if rows is None else rows)
+    # residual groups share one Q vector (synth_q_values): a targeted row's Q is written to the whole group
+    group = {L.index: {L.index} for L in plan}
+    for L in plan:
+        if L.add_src >= 0 and not plan[L.add_src].ipool and L.index in qpos and L.add_src in qpos:
+            g = group[L.index] | group[L.add_src]
+            for m in g:
+                group[m] = g
+
+    done = set()
+
+    def set_q(l, vals):
+        if l in done:                                          # (a residual group takes the Q of its first targeted row)
+            return
+        for m in group[l]:
+            q[qpos[m]] = vals
+        done.update(group[l])
+
+    def q_in(L):
+        """The file Q values of the row's input channels (through pool rows, which keep their input's Q; concat tensors by member)."""
+        src = L.src
+        while src >= 0 and src not in qpos:
+            src = plan[src].src
+        if src == -1:
+            return q[:3].astype(np.int64)
+        if src >= 0:
+            return q[qpos[src]].astype(np.int64)
+        qi = np.zeros(L.C, np.int64)
+        for M in plan:
+            if M.concat == -(src + 2) and M.index in qpos:
+                qi[M.n_start:M.n_start + M.N] = q[qpos[M.index]]
+        return qi
+
+    if regime == "spread":
+        # the producers of the targeted rows get per-channel Q 0 .. 13 (first, in table order: the targeted rows read them)
+        for l in sorted(targets):
+            L = plan[l]
+            if L.src >= 0 and L.src in qpos and len(group[L.src]) == 1 and not plan[L.src].ipool:
+                set_q(L.src, rng.integers(0, 14, size=plan[L.src].N))
+    offs = _stream_offsets(plan)
+    for l in sorted(targets):
+        L = plan[l]
+        if L.ipool or l not in qpos:
+            continue
+        o = offs[l]
+        fan = L.model_C * L.model_k * L.model_k
+        qi = q_in(L)
+        if regime == "wrap":
+            # (a row that reads a boosted tensor drops 8 below it -- expand 7, outputs in range -- so that the row behind can be boosted again)
+            boosted = qi.max() < 8
+            set_q(l, np.full(L.N, min(int(qi.max()) + 10, 14) if boosted else max(int(qi.max()) - 8, 0)))
+            lev = rng.integers(0, 4, size=(L.N, fan))
+            zero = rng.random((L.N, fan)) < 0.05
+        elif regime == "expand32":
+            if L.src >= 0 and L.src in qpos and L.src not in targets:
+                for m in group[L.src]:
+                    q[qpos[m].start] = -3
+                qi = q_in(L)
+            set_q(l, np.full(L.N, 14))
+            lev = rng.integers(0, 4, size=(L.N, fan))
+            zero = rng.random((L.N, fan)) < 0.05
+        elif regime in ("shift22", "shift23"):
+            set_q(l, np.full(L.N, int(qi.min()) + (7 if regime == "shift22" else 8)))
+            lev = rng.integers(0, 7, size=(L.N, fan))
+            lev[:, 0] = 0
+            zero = rng.random((L.N, fan)) < 0.1
+            zero[:, 0] = False
+        elif regime == "spread":
+            lev = rng.integers(0, 15, size=(L.N, fan))
+            if L.N > 64:
+                lev[64:128] = rng.integers(10, 15, size=(min(L.N, 128) - 64, fan))
+            zero = rng.random((L.N, fan)) < 0.1
+            zero[0] = True; zero[0, fan // 2] = False        # one non-zero tap
+            zero[1] = True                                     # all-zero row
+            if l + 1 < len(plan) and not plan[l + 1].ipool and l + 1 not in targets and offs[l + 1]["w"] is not None:
+                M = plan[l + 1]
+                fan2 = M.model_C * M.model_k * M.model_k
+                lev2 = rng.integers(0, 8, size=(M.N, fan2))
+                sign2 = np.where(rng.random((M.N, fan2)) < 0.5, -1.0, 1.0)
+                w2 = np.ldexp(sign2, -lev2) * 2.0 ** -3
+                w2[rng.random((M.N, fan2)) < 0.1] = 0.0
+                model[offs[l + 1]["w"]:offs[l + 1]["w"] + M.N * fan2] = w2.astype(np.float32).ravel()
+        else:                                                  # saturate: the filters stay INQ-like
+            lev = None
+        if lev is not None:
+            sign = np.where(rng.random((L.N, fan)) < 0.5, -1.0, 1.0)
+            w = np.ldexp(sign, -lev)
+            w[zero] = 0.0
+            model[o["w"]:o["w"] + L.N * fan] = w.astype(np.float32).ravel()
+        qo = q[qpos[l]].astype(np.int64)
+        if o["gamma"] is None:
+            if regime == "saturate" and o["bias"] is not None:
+                model[o["bias"]:o["bias"] + L.N] = (rng.choice([-1.0, 1.0], L.N) * rng.uniform(2.0, 6.0, L.N)).astype(np.float32)
+            continue
+        n = np.arange(L.N)
+        mean = np.zeros(L.N); var = np.ones(L.N)
+        if regime == "wrap":
+            semi = boosted and l % 2 == 0
+            gamma = np.ldexp(rng.uniform(1.0, 4.0, L.N), -9) if semi else rng.uniform(1.0, 4.0, L.N)
+            beta = rng.uniform(-0.5, 0.5, L.N)
+        elif regime == "saturate":
+            var0 = model[o["var"]:o["var"] + L.N].astype(np.float64)
+            mean = model[o["mean"]:o["mean"] + L.N].astype(np.float64)
+            var = var0
+            gamma = rng.uniform(32.0, 128.0, L.N)
+            beta = rng.choice([-1.0, 1.0], L.N) * rng.uniform(0.0, 128.0, L.N) * 2.0 ** -qo
+            if not L.relu and L.add_src >= 0:
+                beta = -rng.uniform(300.0, 3000.0, L.N) * 2.0 ** -qo           # y far below -128 (in output units)
+            # all-zero rows whose x = beta_fix sits where x + 2^14 saturates (and its mirror at the bottom)
+            edge = n[::8]
+            zrow = np.zeros((L.N, fan), bool); zrow[edge] = True
+            cur = model[o["w"]:o["w"] + L.N * fan].reshape(L.N, fan)
+            cur[zrow] = 0.0
+            mean[edge] = 0.0; var[edge] = 1.0; gamma[edge] = 1.0
+            top = np.where(np.arange(edge.size) % 2 == 0, 2.0 ** 31 - 2.0 ** 13, -(2.0 ** 31) + 2.0 ** 13)
+            beta[edge] = top / 2.0 ** (15 + qo[edge])
+            if o["bias"] is not None:
+                model[o["bias"] + edge] = 0.0
+        else:
+            gamma = rng.uniform(0.5, 1.5, L.N) * 2.0 ** -8
+            beta = rng.uniform(-0.5, 0.5, L.N)
+        model[o["mean"]:o["mean"] + L.N] = mean.astype(np.float32)
+        model[o["var"]:o["var"] + L.N] = var.astype(np.float32)
+        model[o["gamma"]:o["gamma"] + L.N] = gamma.astype(np.float32)
+        model[o["beta"]:o["beta"] + L.N] = beta.astype(np.float32)
+    assert model.size == cfg.model_float_count(tables)
+    return q, model
+
+
+def synth_extreme_images(tables: cfg.NetTables, batch: int, seed: int = 0) -> np.ndarray:
+    """int8 images, uniform over the whole range, with -128 and 127 patches (the negate quirk and the largest magnitudes)."""
+    x = synth_images(tables, batch, seed, kind="int8")
+    h = x.shape[2]
+    x[:, :, : max(1, h // 8), :] = -128
+    x[:, :, h // 2: h // 2 + max(1, h // 8), :] = 127
+    return x
