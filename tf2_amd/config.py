@@ -938,3 +938,93 @@ def tiny_tables(hw: int = 12, c0: int = 3, widths=(16, 32), classes: int = 10) -
     y = b.conv(y, w0, h2, h2, w1, 1, 1, 0, relu=0, add=x, add_relu=1, endpool=1, endpool_hw=h2 * h2)
     b.conv(y, w1, 1, 1, classes, 1, 1, 0, relu=0, bn=0, bias=1)
     return b.tables()
+
+
+# ---- post-op programs: max pools behind rows without ReLU, pooling rows on signed tensors, pool + global average rows, global averages
+# on small and large maps (tests/test_postop_extremes.py).  Pool geometries (S, stride, pad, ceil mode) as the kernels take them.
+POOL_GEOMS = {"3s2p1": (3, 2, 1, False), "3s2p0c": (3, 2, 0, True), "2s2p0e": (2, 2, 0, False), "2s2p0o": (2, 2, 0, True)}
+
+
+def pool_out(h: int, S: int, st: int, pad: int, ceil: bool) -> int:
+    """Pooled size of an h-pixel side (ceil mode: a last window that reaches past the map, zero-extended by pool.cl:119-140)."""
+    return (h + 2 * pad - S + (st - 1 if ceil else 0)) // st + 1
+
+
+def with_flags(t: NetTables, key: str, rows, value: int) -> NetTables:
+    """A copy of the tables with t[key][l] = value for every l in rows (e.g. kReluEnable = 0 under a pooled row)."""
+    out = NetTables({k: (list(v) if isinstance(v, list) else v) for k, v in t.items()})
+    for l in rows:
+        out[key][l] = int(value)
+    return out.validate()
+
+
+def signed_pool_tables(geom: str = "3s2p1", relu: int = 0, hw: int = 16, ipool=(3, 1, 1)) -> NetTables:
+    """Row 1 (3x3, pad 1, ReLU = `relu`) pooled in geometry `geom` (POOL_GEOMS; "2s2p0o" runs on the odd map hw - 1), row 3 a pooling
+    row (kIpoolEnable) of geometry `ipool` on row 2, a 1x1 row without ReLU: the max pools of signed maps, then a global average and a
+    classifier."""
+    S, st, pad, ceil = POOL_GEOMS[geom]
+    h = hw - 1 if geom == "2s2p0o" else hw
+    b = _B(f"signed_pool_{geom}", image=(3, h, h), first_filter=3)
+    a = b.conv(-1, 3, h, h, 32, 3, 1, 1, relu=1)
+    ph = pool_out(h, S, st, pad, ceil)
+    p = b.conv(a, 32, h, h, 64, 3, 1, 1, relu=relu, pool=(S, st, pad, ph, ph))
+    s = b.conv(p, 64, ph, ph, 64, 1, 1, 0, relu=0)
+    S2, st2, pad2 = ipool
+    ph2 = pool_out(ph, S2, st2, pad2, False)
+    i = b.pool_only(s, 64, ph, ph, (S2, st2, pad2, ph2, ph2))
+    y = b.conv(i, 64, ph2, ph2, 32, 1, 1, 0, relu=1, endpool=1, endpool_hw=ph2 * ph2)
+    b.conv(y, 32, 1, 1, 10, 1, 1, 0, relu=0, bn=0, bias=1)
+    return b.tables()
+
+
+def c3_pool_tables(hw: int = 31, relu: int = 1) -> NetTables:
+    """A 3x3 / pad 1 row on 64 channels of an hw x hw map with the 2x2 / 2 pool in ceil mode (an odd hw: the right and bottom windows
+    reach past the map), the form conv_c3's fused POOL takes behind a ReLU; ReLU = `relu` on that row."""
+    ph = pool_out(hw, 2, 2, 0, True)
+    b = _B("c3_pool", image=(3, hw, hw), first_filter=3)
+    a = b.conv(-1, 3, hw, hw, 64, 3, 1, 1, relu=1)
+    p = b.conv(a, 64, hw, hw, 64, 3, 1, 1, relu=relu, pool=(2, 2, 0, ph, ph))
+    y = b.conv(p, 64, ph, ph, 64, 1, 1, 0, relu=1, endpool=1, endpool_hw=ph * ph)
+    b.conv(y, 64, 1, 1, 10, 1, 1, 0, relu=0, bn=0, bias=1)
+    return b.tables()
+
+
+def pool_avg_tables(hw: int = 12, relu: int = 1) -> NetTables:
+    """A row that pools AND averages (kPoolEnable = kEndPoolEnable = 1: the global average of the POOLED map, full_size_pool.cl:71-92
+    over kPoolOutputHeight x kPoolOutputWidth): 3x3 first row with the 3/2/1 pool, a 1x1 row, a 1x1 row (ReLU = `relu`) pooled 3/2/1
+    and averaged, a classifier."""
+    h = pool_out(hw, 3, 2, 1, False)
+    h2 = pool_out(h, 3, 2, 1, False)
+    b = _B("pool_avg", image=(3, hw, hw), first_filter=3)
+    a = b.conv(-1, 3, hw, hw, 32, 3, 1, 1, relu=1, pool=(3, 2, 1, h, h))
+    x = b.conv(a, 32, h, h, 64, 1, 1, 0, relu=1)
+    y = b.conv(x, 64, h, h, 64, 1, 1, 0, relu=relu, pool=(3, 2, 1, h2, h2), endpool=1, endpool_hw=h2 * h2)
+    b.conv(y, 64, 1, 1, 10, 1, 1, 0, relu=0, bn=0, bias=1)
+    return b.tables()
+
+
+def stem_pool_avg_tables(relu: int = 1) -> NetTables:
+    """ResNet-50's first row (the 7x7 / 2 conv as its 27-channel 3x3 form on the 224 x 224 image, the 3/2/1 pool: conv_stem's fused
+    pool) with a global average of the pooled 56 x 56 map in the same row, then a classifier."""
+    b = _B("stem_pool_avg", image=(3, 224, 224), first_filter=7, rewrite=1)
+    a = b.conv(-1, 27, 114, 114, 64, 3, 1, 0, relu=relu, pool=(3, 2, 1, 56, 56), endpool=1, endpool_hw=56 * 56)
+    b.conv(a, 64, 1, 1, 10, 1, 1, 0, relu=0, bn=0, bias=1)
+    return b.tables()
+
+
+def avg_tables(hw: int = 22, n: int = 64, mult: Optional[int] = None) -> NetTables:
+    """A global average without ReLU on an hw x hw map, behind the rows that let its input be set exactly (synth.synth_postop
+    "avg_extreme"): row 1 a 1x1 row, row 2 a 3x3 / pad 1 row with ReLU, row 3 the averaged 1x1 row, then a classifier.  hw <= 8: the split-K
+    kernel's fused average (conv_mfma_sk AVG); hw >= 17: global_avg_kernel, whose int16 sum can wrap.  mult: the average's multiplier
+    (default round(2^15 / hw^2)).  With round(2^15 / HW) no average can clip; with the reference's hard-wired 669
+    (full_size_pool.cl:118, exact for 7 x 7 only) on a larger map both ends clip."""
+    b = _B(f"avg_{hw}" + (f"_m{mult}" if mult else ""), image=(3, hw, hw), first_filter=3)
+    a = b.conv(-1, 3, hw, hw, 32, 3, 1, 1, relu=1)
+    k = b.conv(a, 32, hw, hw, n, 1, 1, 0, relu=0)
+    p = b.conv(k, n, hw, hw, n, 3, 1, 1, relu=1)          # (an unsigned input: the averaged row runs on the MFMA kernels)
+    y = b.conv(p, n, hw, hw, n, 1, 1, 0, relu=0, endpool=1, endpool_hw=hw * hw)
+    b.conv(y, n, 1, 1, 10, 1, 1, 0, relu=0, bn=0, bias=1)
+    t = b.tables()
+    if mult:
+        t["xEndPoolMult"][y] = int(mult)
+    return t

@@ -81,6 +81,8 @@ tf2_status Net::init(const tf2_net_desc* d, const tf2_layer_desc* ls) {
     if (L.n_start < 0 || L.n_start + L.N > nd.max_out_channel) { set_error("layer " + std::to_string(l) + ": n_start + N exceeds MAX_OUT_CHANNEL"); return TF2_ERR_ARG; }
     if (L.concat >= 0 && nd.n_conv + 1 + L.concat >= nd.n_q_rows) { set_error("layer " + std::to_string(l) + ": concat Q row outside the q table"); return TF2_ERR_ARG; }
     if (L.pool_en && L.add_src >= 0) { set_error("layer " + std::to_string(l) + ": pool + residual in one layer is not supported"); return TF2_ERR_UNSUPPORTED; }
+    // (a pooling row's global average: the oracle and netref define none -- tf2o_layer averages a CONV row's pooled map only)
+    if (L.ipool == 1 && L.endpool) { set_error("layer " + std::to_string(l) + ": a pool-only row with a global average is not supported"); return TF2_ERR_UNSUPPORTED; }
     out_Cp[l] = round_up(L.N, 16);
     InLayout il;
     int srcC, srcH, srcW;
@@ -173,6 +175,12 @@ const WorkPlan* Net::plan(int batch, bool keep_all) {
       E.conv_tensor = add_tensor(th, tw, Nx, round_up(Nx, 16));
       born.push_back(l);
       wp.tensors[E.conv_tensor].last_use = l;
+      // pool + global average: conv map -> pooled map (this tensor) -> 1 x 1 output (maxpool_kernel, then global_avg_kernel)
+      if (L.pool_en && L.endpool) {
+        E.pool_tensor = add_tensor(L.PH, L.PW, L.N, out_Cp[l]);
+        born.push_back(l);
+        wp.tensors[E.pool_tensor].last_use = l;
+      }
     }
     if (L.add_src >= 0) {
       E.res_tensor = layer_out[L.add_src];
@@ -661,10 +669,10 @@ const LaunchPlan* Net::launch_plan(int batch, const WorkPlan* wp, void* ws, bool
     const LayerExec& E = wp->exec[l];
     Launch st; st.kind = Launch::POOL; st.layer = l;
     PoolArgs& pa = st.pool;
-    const TensorPlan& to = T(E.out_tensor);
+    const TensorPlan& to = T(E.pool_tensor >= 0 ? E.pool_tensor : E.out_tensor);
     pa.x = x; pa.y = base + to.offset;
     pa.B = batch; pa.H = H; pa.W = W; pa.x_cp = ti.Cp; pa.x_off = 0;
-    pa.PH = L.PH; pa.PW = L.PW; pa.y_cp = to.Cp; pa.y_off = E.out_off;
+    pa.PH = L.PH; pa.PW = L.PW; pa.y_cp = to.Cp; pa.y_off = E.pool_tensor >= 0 ? 0 : E.out_off;
     pa.S = L.pool_S; pa.st = L.pool_st; pa.pad = L.pool_pad; pa.C16 = round_up(L.N, 16) / 16;
     lp.steps.push_back(st);
   };
@@ -1225,12 +1233,17 @@ const LaunchPlan* Net::launch_plan(int batch, const WorkPlan* wp, void* ws, bool
     const TensorPlan& tc = T(E.conv_tensor);
     if (L.pool_en && !(l == 0 && stem_pool_fused) && !(c3_pool_fused && st.sel == Launch::SEL_C3)) {
       pool_step(l, tc, base + tc.offset, L.OH, L.OW);
-    } else if (L.endpool && !st.avg_fused) {
+    }
+    // (no fused pool takes a row that averages as well: conv_stem's image is not packed for it -- weight_pack.cpp --, c3_at, fire_at and
+    //  the conv_first form refuse it, and the split-K / group averages read the conv map)
+    if (L.endpool && !st.avg_fused) {
+      // (a row that pools as well averages its pooled map: full_size_pool.cl:71-92 reads pool_tail's PH x PW output)
       Launch sa; sa.kind = Launch::AVG; sa.layer = l;
       AvgArgs& aa = sa.avg;
       const TensorPlan& to = T(E.out_tensor);
-      aa.x = base + tc.offset; aa.y = base + to.offset;
-      aa.B = batch; aa.HW = L.PH * L.PW; aa.x_cp = tc.Cp; aa.x_off = 0;
+      const TensorPlan& ta = L.pool_en ? T(E.pool_tensor) : tc;
+      aa.x = base + ta.offset; aa.y = base + to.offset;
+      aa.B = batch; aa.HW = L.PH * L.PW; aa.x_cp = ta.Cp; aa.x_off = 0;
       aa.y_cp = to.Cp; aa.y_off = E.out_off; aa.C = round_up(L.N, 16); aa.mult = L.endpool_mult;
       lp.steps.push_back(sa);
     }

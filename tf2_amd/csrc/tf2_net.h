@@ -25,6 +25,7 @@ struct LayerExec {
   int in_tensor = -1;      // tensor ids into WorkPlan::tensors
   int out_tensor = -1;     // final output of the layer (own tensor or concat tensor)
   int conv_tensor = -1;    // where the conv kernel writes (== out_tensor unless pool/endpool)
+  int pool_tensor = -1;    // a row that pools AND averages: the PH x PW pooled map the average reads (full_size_pool.cl:71-92)
   int res_tensor = -1;
   int res_off = 0;
   int out_off = 0;         // channel offset inside out_tensor (concat slice)

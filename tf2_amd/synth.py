@@ -368,3 +368,156 @@ def synth_extreme_images(tables: cfg.NetTables, batch: int, seed: int = 0) -> np
     x[:, :, : max(1, h // 8), :] = -128
     x[:, :, h // 2: h // 2 + max(1, h // 8), :] = 127
     return x
+
+
+# ---- post-op regimes: the maps that max pools and global averages read, set so that their edges are reached --------------------------
+POSTOP_REGIMES = ("signed_pool", "avg_extreme")
+
+
+def avg_of_sum(s: int, mult: int) -> int:
+    """The global average of an int16 sum before the clip (full_size_pool.cl:118)."""
+    return (((s * mult) >> 14) + 1) >> 1
+
+
+def _wrap16(s: int) -> int:
+    return (s + 32768) % 65536 - 32768
+
+
+def avg_level_targets(H: int, W: int, mult: int) -> Dict[str, List[tuple]]:
+    """Every pair (A, B) of int8 levels with A - B an int8 as well, by what the global average of an H x W map that holds A on the
+    (H - 1) x (W - 1) pixels with row and column > 0 and B on the rest makes of it (full_size_pool.cl:101-118: int16 sum, then
+    ((s * mult) >> 14) + 1 >> 1, then the clip).  Categories: half+ / half- (s * mult an odd multiple of 2^14: the rounding half, by
+    the sign of s), clip+ / clip-, wrap+ / wrap- (the int16 sum wraps; by the sign of the true sum), neg (a negative average that is none
+    of those)."""
+    nA, nB = (H - 1) * (W - 1), H + W - 1
+    out: Dict[str, List[tuple]] = {k: [] for k in ("half+", "half-", "clip+", "clip-", "wrap+", "wrap-", "neg")}
+    for A in range(-128, 128):
+        for B in range(max(-128, A - 127), min(127, A + 128) + 1):
+            st = A * nA + B * nB
+            s = _wrap16(st)
+            m = avg_of_sum(s, mult)
+            half = (s * mult) % 32768 == 16384
+            if half:
+                out["half+" if s > 0 else "half-"].append((A, B))
+            if m > 127:
+                out["clip+"].append((A, B))
+            if m < -128:
+                out["clip-"].append((A, B))
+            if st != s:
+                out["wrap+" if st > 0 else "wrap-"].append((A, B))
+            if -128 <= m < 0 and not half and st == s and (s * mult) % 16384:
+                out["neg"].append((A, B))
+    return out
+
+
+def _bn_const(model, o, n, v, qo, fan):
+    """Channel n of a row: an output of exactly v everywhere.  With BN: mean 0, variance 1, gamma 2^-24 (alpha_fix = 0: the filters,
+    left as they are, drop out) and beta v * 2^-Q (beta_fix = v << 15); without BN: all-zero filters and bias v * 2^-Q."""
+    if o["gamma"] is not None:
+        model[o["mean"] + n] = 0.0; model[o["var"] + n] = 1.0; model[o["gamma"] + n] = 2.0 ** -24
+        model[o["beta"] + n] = np.float32(v * 2.0 ** -qo)
+    else:
+        model[o["w"] + n * fan:o["w"] + (n + 1) * fan] = 0.0
+        model[o["bias"] + n] = np.float32(v * 2.0 ** -qo)
+
+
+def synth_postop(tables: cfg.NetTables, seed: int, regime: str, rows=None):
+    """(q_values, model_stream) in the formats of synth_q_values / synth_model: synth_q_values(spread=1) and synth_model, with the rows
+    `rows` set so that the post-op behind them reaches its edges.
+
+    signed_pool  rows: the pooled conv rows and the producers of pooling rows (default: all).  Channel n % 8 of a row: 0 all -128, 1 all
+                 127, 2 one negative value everywhere (zero filters, the value from beta), 3 negative almost everywhere with the filters'
+                 texture (gamma / 4, beta -80 output units), 4 saturated at both ends (gamma x 64); the rest as drawn.  (Constant channels keep
+                 their filters where the row has BN: alpha_fix = 0 -- conv_stem's packed form needs the rewrite's unit taps in every row.)  Behind a row
+                 without ReLU: every window whose inside is negative -- the whole map of channels 0, 2 -- is decided by the zero taps of
+                 the padding / the ceil-mode edge, or by the zero slot of a window narrower than 3 (pool.cl:115-140, 177-186).
+    avg_extreme  rows: averaged rows (default: all).  Where the averaged row R is a 1x1 row over a 3x3 / pad 1 row P over a conv row K
+                 (same channels, all with BN, no residual: cfg.avg_tables), channel n of R is made a two-level map: K's channel n the
+                 constant A - B, P's one tap (0, 0) of weight 1 on it plus B (so A where the tap is inside the map, B on the first row
+                 and column), R the identity (P and R take K's Q); behind a P with ReLU the levels A - C, B - C with R's beta C =
+                 min(A, B, 0).  The levels are drawn per channel from avg_level_targets: int16
+                 wraps, rounding halves of both signs, clips at both ends and negative averages, whichever the map size admits; every
+                 fourth channel keeps its texture.  Elsewhere (a residual row, ResNet-50's row 52) the averaged row's channels n % 4 = 0,
+                 1, 2 get the constant outputs -128, 127 and a negative value (the residual adds on top).
+    """
+    assert regime in POSTOP_REGIMES, regime
+    rng = np.random.default_rng(9000 + seed)
+    plan = cfg.build_plan(tables)
+    q = synth_q_values(tables, seed, spread=1).astype(np.int32)
+    model = synth_model(tables, q, seed).astype(np.float32)
+    qpos, _ = _q_layout(tables, plan)
+    offs = _stream_offsets(plan)
+
+    def fan(L):
+        return L.model_C * L.model_k * L.model_k
+
+    def zero_filters(l, n):
+        L = plan[l]
+        model[offs[l]["w"] + n * fan(L):offs[l]["w"] + (n + 1) * fan(L)] = 0.0
+
+    if regime == "signed_pool":
+        if rows is None:
+            rows = [L.index for L in plan if L.pool_en and not L.ipool] + [L.src for L in plan if L.ipool == 1 and L.src >= 0 and not plan[L.src].ipool]
+        for l in sorted(set(rows)):
+            L, o = plan[l], offs[l]
+            qo = q[qpos[l]].astype(np.int64)
+            for n in range(L.N):
+                cls = n % 8
+                if cls in (0, 1, 2):
+                    _bn_const(model, o, n, (-128, 127, int(rng.integers(-127, 0)))[cls], qo[n], fan(L))
+                elif cls == 3:
+                    if o["gamma"] is not None:
+                        g = model[o["gamma"] + n] * 0.25
+                        b = np.sqrt(model[o["var"] + n] + 1e-5)
+                        model[o["gamma"] + n] = g
+                        model[o["beta"] + n] = np.float32(-80.0 * 2.0 ** -qo[n] + g / b * model[o["mean"] + n])
+                    else:
+                        model[o["bias"] + n] = np.float32(-80.0 * 2.0 ** -qo[n])
+                elif cls == 4 and o["gamma"] is not None:
+                    model[o["gamma"] + n] *= 64.0
+        assert model.size == cfg.model_float_count(tables)
+        return q, model
+
+    if rows is None:
+        rows = [L.index for L in plan if L.endpool]
+    for l in sorted(set(rows)):
+        R = plan[l]
+        P = plan[R.src] if R.src >= 0 else None
+        K = plan[P.src] if P is not None and P.src >= 0 else None
+        chain = (K is not None and not K.ipool and not P.ipool and R.k == 1 and R.stride == 1 and P.k == 3 and P.stride == 1 and
+                 P.pad_h == 1 and P.pad_w == 1 and P.dil == 1 and R.N == P.N == K.N == R.C == P.C and R.add_src < 0 and P.add_src < 0 and
+                 not (P.pool_en or P.endpool or K.pool_en or K.endpool or R.pool_en) and K.concat < 0 and P.concat < 0 and
+                 all(offs[m.index]["gamma"] is not None for m in (R, P, K)) and
+                 not any(M.add_src in (R.index, P.index, K.index) for M in plan))
+        if not chain:
+            qo = q[qpos[l]].astype(np.int64)
+            for n in range(R.N):
+                if n % 4 < 3:
+                    _bn_const(model, offs[l], n, (-128, 127, int(rng.integers(-127, 0)))[n % 4], qo[n], fan(R))
+            continue
+        qk = q[qpos[K.index]].copy()
+        q[qpos[P.index]] = qk
+        q[qpos[R.index]] = qk
+        H, W = R.H, R.W
+        lv = avg_level_targets(H, W, R.endpool_mult)
+        if P.relu:          # (P's levels non-negative: R's beta C = min(A, B, 0) moves them back)
+            lv = {k: [(A, B) for A, B in v if max(A, B, 0) - min(A, B, 0) <= 127] for k, v in lv.items()}
+        cats = [(k, v) for k, v in lv.items() if v]
+        ok, op, orr = offs[K.index], offs[P.index], offs[R.index]
+        for n in range(R.N):
+            if n % 4 == 3:
+                continue
+            _, cand = cats[(n - n // 4) % len(cats)]
+            A, B = cand[int(rng.integers(0, len(cand)))]
+            C = min(A, B, 0) if P.relu else 0
+            _bn_const(model, ok, n, A - B, qk[n], fan(K))
+            for M, o, beta in ((P, op, B - C), (R, orr, C)):
+                zero_filters(M.index, n)
+                tap = 0 if M is P else (M.model_k * M.model_k) // 2
+                model[o["w"] + n * fan(M) + n * M.model_k * M.model_k + tap] = 1.0
+                model[o["mean"] + n] = 0.0; model[o["var"] + n] = 1.0; model[o["gamma"] + n] = 1.0
+                model[o["beta"] + n] = np.float32(beta * 2.0 ** -qk[n])
+                if o["bias"] is not None:
+                    model[o["bias"] + n] = 0.0
+    assert model.size == cfg.model_float_count(tables)
+    return q, model
