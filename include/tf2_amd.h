@@ -235,6 +235,50 @@ tf2_status tf2_net_profile_loop_read(tf2_net* net, float* ms_total, int32_t* run
 tf2_status tf2_net_profile_read(tf2_net* net, float* ms_per_layer, int32_t* launches_per_layer,
                                 int32_t* kernel_kind_per_layer, int capacity);
 
+/* ---- SSD detection on the device (detection.py:27-62, box_utils.py:140-158 decode, :175-239 nms; INTEGRATION.md "SSD detection") ----
+ * A detector belongs to a network handle (after pack / adopt; it reads the handle's q table and packed image at create: a later
+ * set_q / pack needs a new detector).  tf2_ssd_create checks on the host, before any device call: every loc row has N = 4 * nb, the
+ * conf row of the same source N = nb * num_classes on the same map, both are sinks (no row reads them) and not concat members,
+ * sum over sources of H * W * nb == n_priors, num_classes in 2..256, top_k in 1..256, nms_thresh > 0, conf_thresh >= 0, n_priors
+ * <= 32768; a failure is TF2_ERR_ARG with a message.  The handle holds read-only device constants (priors, the heads' 2^-Q scales);
+ * everything a step writes lives in the caller's workspace, so several streams with their own workspaces run side by side.
+ * Semantics: per image and class >= 1, candidates p > conf_thresh (strict), the best top_k of them by (score descending, prior
+ * index ascending), greedy NMS in that order (a candidate survives unless its IoU with a kept box is > nms_thresh), IoU in IEEE
+ * float32 as ssd._iou_one_to_many evaluates it; rows best first, no cross-class cap.  ssd.detect_ordered is the host statement. */
+typedef struct tf2_ssd tf2_ssd;
+typedef struct tf2_ssd_desc {
+  uint32_t size;                 /* sizeof(tf2_ssd_desc)                                                */
+  int32_t num_classes;           /* 2..256, including background class 0                               */
+  int32_t top_k;                 /* 1..256                                                             */
+  float conf_thresh, nms_thresh; /* >= 0 / > 0 (the reference's test defaults: 0.01 / 0.45)            */
+  float variance[2];             /* 0.1, 0.2                                                           */
+  int32_t n_sources;             /* 1..8 (SSD300: 6)                                                   */
+  int32_t loc_row[8], conf_row[8];
+  const float* priors;           /* host, [n_priors][4] centre form (ssd.prior_boxes); copied          */
+  int32_t n_priors;
+} tf2_ssd_desc;
+tf2_status tf2_ssd_create(tf2_net* net, const tf2_ssd_desc* d, tf2_ssd** out);
+void       tf2_ssd_destroy(tf2_ssd* s);
+/* workspace of tf2_ssd_run: the "outputs kept" plan of `batch` images (the ordinary plan, but every sink row's output lives to the
+ * end of the step and the last row is not stored straight into the logits) + the detector's boxes and probabilities */
+size_t     tf2_ssd_workspace_size(tf2_ssd* s, int batch);
+/* scratch of tf2_ssd_detect: the probabilities transposed to class-major order */
+size_t     tf2_ssd_detect_scratch_size(tf2_ssd* s, int batch);
+/* One step: the network on the outputs-kept plan, then heads -> boxes + probabilities (dequantise, float32 softmax, decode) and
+ * select + NMS, all enqueued on hip_stream (no host synchronisation, no allocation: graph-capturable).
+ * det [batch][num_classes][top_k][5] float32 (score, x1, y1, x2, y2; rows past counts[b][c] and class 0 are zero), counts
+ * [batch][num_classes] int32.  Optional (NULL): boxes_out [batch][n_priors][4] / scores_out [batch][n_priors][num_classes] float32,
+ * the decoded corner-form boxes and class probabilities the selection worked on; logits_out, the network's int8 logits as
+ * tf2_net_run writes them; mark_event, a hipEvent_t recorded on hip_stream between the network's launches and the detector's (timing:
+ * tools/ssd_detect_time.py).  tf2_net_poll_error works on the workspace afterwards as after tf2_net_run. */
+tf2_status tf2_ssd_run(tf2_ssd* s, const void* images_dev, int images_are_q, int batch, void* workspace_dev, size_t workspace_bytes,
+                       float* det_dev, int32_t* counts_dev, float* boxes_out, float* scores_out, int8_t* logits_out, void* mark_event,
+                       void* hip_stream);
+/* The selection alone, on the caller's corner-form boxes [batch][n_priors][4] and class probabilities [batch][n_priors][num_classes]
+ * (device, float32); det / counts as above. */
+tf2_status tf2_ssd_detect(tf2_ssd* s, const float* boxes_dev, const float* scores_dev, int batch, void* scratch_dev,
+                          size_t scratch_bytes, float* det_dev, int32_t* counts_dev, void* hip_stream);
+
 /* ---- Evaluation (network_helper.cpp:143-207): top-k with the reference's tie rule ---- */
 tf2_status tf2_topk(const int8_t* logits, const int8_t* q_last_row, int n, int k,
                     int32_t* labels, float* features);

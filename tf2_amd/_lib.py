@@ -55,6 +55,13 @@ class RowTensors(C.Structure):
     _fields_ = [("in_tensor", C.c_int32), ("out_tensor", C.c_int32), ("conv_tensor", C.c_int32), ("res_tensor", C.c_int32)]
 
 
+class SsdDesc(C.Structure):
+    """tf2_ssd_desc (include/tf2_amd.h)."""
+    _fields_ = [("size", C.c_uint32), ("num_classes", C.c_int32), ("top_k", C.c_int32), ("conf_thresh", C.c_float),
+                ("nms_thresh", C.c_float), ("variance", C.c_float * 2), ("n_sources", C.c_int32), ("loc_row", C.c_int32 * 8),
+                ("conf_row", C.c_int32 * 8), ("priors", C.c_void_p), ("n_priors", C.c_int32)]
+
+
 class NetDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "n_layers", "n_conv", "n_q_rows", "max_out_channel", "image_c", "image_h", "image_w",
@@ -137,6 +144,15 @@ def lib() -> C.CDLL:
     L.tf2_net_profile_read.argtypes = [vp, vp, vp, vp, C.c_int]
     L.tf2_net_profile_loop_read.argtypes = [vp, vp, vp]
     L.tf2_topk.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
+    L.tf2_ssd_create.argtypes = [vp, C.POINTER(SsdDesc), C.POINTER(vp)]
+    L.tf2_ssd_destroy.argtypes = [vp]
+    L.tf2_ssd_destroy.restype = None
+    L.tf2_ssd_workspace_size.argtypes = [vp, C.c_int]
+    L.tf2_ssd_workspace_size.restype = sz
+    L.tf2_ssd_detect_scratch_size.argtypes = [vp, C.c_int]
+    L.tf2_ssd_detect_scratch_size.restype = sz
+    L.tf2_ssd_run.argtypes = [vp, vp, C.c_int, C.c_int, vp, sz, vp, vp, vp, vp, vp, vp, vp]
+    L.tf2_ssd_detect.argtypes = [vp, vp, vp, C.c_int, vp, sz, vp, vp, vp]
     _lib = L
     return L
 
@@ -146,7 +162,8 @@ EXPORTED = [
     "tf2_net_create", "tf2_net_destroy", "tf2_net_set_q", "tf2_net_load_model", "tf2_model4bit_decode", "tf2_net_load_model_4bit", "tf2_net_get_codes",
     "tf2_net_get_bias_bn", "tf2_net_pack", "tf2_net_packed_size", "tf2_net_packed_copy",
     "tf2_net_packed_adopt", "tf2_net_bind_device", "tf2_net_workspace_size", "tf2_net_logits_size", "tf2_net_reload_options", "tf2_net_run",
-    "tf2_net_run_q", "tf2_net_run_ex", "tf2_net_run_stats", "tf2_net_poll_error", "tf2_net_describe_launches", "tf2_net_describe_workspace", "tf2_net_read_layer", "tf2_net_profile", "tf2_net_profile_read", "tf2_net_profile_loop_read", "tf2_topk"]
+    "tf2_net_run_q", "tf2_net_run_ex", "tf2_net_run_stats", "tf2_net_poll_error", "tf2_net_describe_launches", "tf2_net_describe_workspace", "tf2_net_read_layer", "tf2_net_profile", "tf2_net_profile_read", "tf2_net_profile_loop_read", "tf2_topk",
+    "tf2_ssd_create", "tf2_ssd_destroy", "tf2_ssd_workspace_size", "tf2_ssd_detect_scratch_size", "tf2_ssd_run", "tf2_ssd_detect"]
 
 
 def parse_opts(text: str) -> dict:

@@ -4,10 +4,12 @@
 #include "tf2_net.h"
 #include "tf2_device.h"
 #include "opts.h"
+#include "ssd_detect.h"
 
 using namespace tf2;
 
 struct tf2_net { Net impl; };
+struct tf2_ssd { SsdDetector impl; };
 
 #define CHECK_NET(n)                                              \
   if (!(n)) { set_error("null tf2_net handle"); return TF2_ERR_ARG; }
@@ -258,6 +260,36 @@ tf2_status tf2_net_describe_workspace(tf2_net* net, int batch, int keep_all, tf2
     rows[i].in_tensor = r[i].in_tensor; rows[i].out_tensor = r[i].out_tensor; rows[i].conv_tensor = r[i].conv_tensor; rows[i].res_tensor = r[i].res_tensor;
   }
   return TF2_OK;
+}
+
+tf2_status tf2_ssd_create(tf2_net* net, const tf2_ssd_desc* d, tf2_ssd** out) {
+  CHECK_NET(net);
+  if (!d || !out) { set_error("tf2_ssd_create: null argument"); return TF2_ERR_ARG; }
+  tf2_ssd* s = new (std::nothrow) tf2_ssd();
+  if (!s) { set_error("out of memory"); return TF2_ERR_SIZE; }
+  const tf2_status st = s->impl.create(&net->impl, d);
+  if (st != TF2_OK) { delete s; return st; }
+  *out = s;
+  return TF2_OK;
+}
+
+void tf2_ssd_destroy(tf2_ssd* s) { delete s; }
+
+size_t tf2_ssd_workspace_size(tf2_ssd* s, int batch) { return s ? s->impl.workspace_size(batch) : 0; }
+
+size_t tf2_ssd_detect_scratch_size(tf2_ssd* s, int batch) { return s ? s->impl.detect_scratch_size(batch) : 0; }
+
+tf2_status tf2_ssd_run(tf2_ssd* s, const void* images_dev, int images_are_q, int batch, void* ws, size_t ws_bytes, float* det_dev,
+                       int32_t* counts_dev, float* boxes_out, float* scores_out, int8_t* logits_out, void* mark_event, void* hip_stream) {
+  if (!s) { set_error("null tf2_ssd handle"); return TF2_ERR_ARG; }
+  return s->impl.run(images_dev, images_are_q != 0, batch, ws, ws_bytes, det_dev, counts_dev, boxes_out, scores_out, logits_out, mark_event,
+                     hip_stream);
+}
+
+tf2_status tf2_ssd_detect(tf2_ssd* s, const float* boxes_dev, const float* scores_dev, int batch, void* scratch, size_t scratch_bytes,
+                          float* det_dev, int32_t* counts_dev, void* hip_stream) {
+  if (!s) { set_error("null tf2_ssd handle"); return TF2_ERR_ARG; }
+  return s->impl.detect(boxes_dev, scores_dev, batch, scratch, scratch_bytes, det_dev, counts_dev, hip_stream);
 }
 
 tf2_status tf2_net_read_layer(tf2_net* net, int layer, int batch, const void* ws, int8_t* host_dst,

@@ -124,12 +124,26 @@ tf2_status Net::init(const tf2_net_desc* d, const tf2_layer_desc* ls) {
 }
 
 // ---- workspace planning: first-fit offsets with liveness-based reuse ---------------
-const WorkPlan* Net::plan(int batch, bool keep_all) {
-  auto key = std::make_pair(batch, keep_all ? 1 : 0);
+// Row l is a sink: no row reads it as src, add_src or through a concat (a network output: SSD's multibox heads, the logits row).
+bool Net::is_sink(int l) const {
+  for (int j = 0; j < nd.n_layers; j++) {
+    const tf2_layer_desc& J = layers[j];
+    if (J.src == l || J.add_src == l) return false;
+    if (J.src <= -2 && layers[l].concat == -(J.src + 2)) return false;
+  }
+  return true;
+}
+
+// mode: PLAN_ORDINARY (liveness reuse), PLAN_KEEP_ALL (every tensor its own memory, fused kernels store their intermediates),
+// PLAN_OUTPUTS (the ordinary plan, but every sink row's output lives to the end of the step and the last row stays in the workspace:
+// tf2_ssd_run reads the heads from it; never chosen by tf2_net_run*)
+const WorkPlan* Net::plan(int batch, int mode) {
+  const bool keep_all = mode == PLAN_KEEP_ALL;
+  auto key = std::make_pair(batch, mode);
   auto it = plans.find(key);
   if (it != plans.end()) return &it->second;
   WorkPlan wp;
-  wp.batch = batch; wp.keep_all = keep_all;
+  wp.batch = batch; wp.keep_all = keep_all; wp.outputs_kept = mode == PLAN_OUTPUTS;
   const int nl = nd.n_layers;
   auto add_tensor = [&](int H, int W, int C, int Cp) {
     TensorPlan t; t.H = H; t.W = W; t.C = C; t.Cp = Cp;
@@ -193,6 +207,9 @@ const WorkPlan* Net::plan(int batch, bool keep_all) {
   }
   wp.final_tensor = layer_out[nl - 1];
   wp.tensors[wp.final_tensor].last_use = nl;
+  if (wp.outputs_kept)
+    for (int l = 0; l < nl; l++)
+      if (is_sink(l)) wp.tensors[wp.exec[l].out_tensor].last_use = nl;
   // Fused pairs (conv_bneck.hip: layer l computes layer fuse_next as well, block by block): everything the launch reads
   // stays live until the LATER layer's index, and everything it writes exists from the EARLIER one -- otherwise the
   // first-fit planner hands the expand's output the memory of the 3x3's input, which other blocks are still reading.
@@ -599,7 +616,7 @@ void Net::load_options() {
   std::vector<std::pair<int, int>> keys;
   for (const auto& kv : plans) keys.push_back(kv.first);
   plans.clear();
-  for (const auto& k : keys) (void)plan(k.first, k.second != 0);
+  for (const auto& k : keys) (void)plan(k.first, k.second);
 }
 
 // Group launches (conv_bgroup.hip) keep eight blocks per image resident together, one block per CU: they need a device of at
@@ -1192,7 +1209,7 @@ const LaunchPlan* Net::launch_plan(int batch, const WorkPlan* wp, void* ws, bool
       }
     }
     // the last layer of a classifier (1x1 map, split-K kernel) stores the dense logits [batch][N] itself: no copy kernel
-    if (l == nl - 1 && !wp->keep_all && st.sel == Launch::SEL_SK && !L.pool_en && !L.endpool && L.concat < 0 &&
+    if (l == nl - 1 && !wp->keep_all && !wp->outputs_kept && st.sel == Launch::SEL_SK && !L.pool_en && !L.endpool && L.concat < 0 &&
         L.PH * L.PW == 1 && (L.N % 16 == 0 || L.N % 16 == 8)) {
       st.conv_direct = st.conv;
       ConvGeom& gd = st.conv_direct.g;
@@ -1393,7 +1410,7 @@ size_t Net::logits_bytes(int batch) const {
 }
 
 tf2_status Net::run(const void* images, bool images_are_q, int batch, void* ws, size_t ws_bytes,
-                    int8_t* logits, void* stream, int concurrency, void* mark_event, int mark_after_layer) {
+                    int8_t* logits, void* stream, int concurrency, void* mark_event, int mark_after_layer, bool outputs_kept) {
   std::unique_lock<std::mutex> lock(run_mutex);
   if (!packed_valid) { set_error("tf2_net_run: no packed image (tf2_net_pack / tf2_net_packed_adopt)"); return TF2_ERR_STATE; }
   if (!packed_dev) { set_error("tf2_net_run: packed image not bound to the device (tf2_net_bind_device)"); return TF2_ERR_STATE; }
@@ -1401,13 +1418,22 @@ tf2_status Net::run(const void* images, bool images_are_q, int batch, void* ws, 
   if (batch <= 0) { set_error("tf2_net_run: batch must be positive"); return TF2_ERR_ARG; }
   // keep_all plans are a superset in size; pick whichever plan fits the caller's buffer
   const WorkPlan* wp = nullptr;
-  {
+  if (outputs_kept) {
+    wp = plan(batch, PLAN_OUTPUTS);                         // (tf2_ssd_run only)
+  } else {
     const WorkPlan* a = plan(batch, false);
     auto itk = plans.find(std::make_pair(batch, 1));
     if (itk != plans.end() && ws_bytes >= itk->second.total_bytes) wp = &itk->second;
     else wp = a;
   }
   if (ws_bytes < wp->total_bytes) { set_error("tf2_net_run: workspace too small"); return TF2_ERR_SIZE; }
+  // which workspaces last ran the outputs-kept plan (poll_error reads that plan's error word there)
+  if (outputs_kept) {
+    if (outputs_ws.size() >= 64 && !outputs_ws.count(ws)) outputs_ws.erase(outputs_ws.begin());
+    outputs_ws[ws] = batch;
+  } else if (!outputs_ws.empty()) {
+    outputs_ws.erase(ws);
+  }
   // batches in flight?  (calls on at least two different streams among the last eight)
   void* const tag = (void*)((uintptr_t)stream + 1);          // the null stream is a stream too; 0 = empty slot
   recent_streams[recent_pos] = tag; recent_pos = (recent_pos + 1) & 7;
@@ -1508,7 +1534,10 @@ tf2_status Net::poll_error(int batch, void* ws, size_t ws_bytes, void* stream) {
   if (!packed_valid || !packed_dev) { set_error("tf2_net_poll_error: no packed model bound"); return TF2_ERR_STATE; }
   if (batch <= 0 || !ws) { set_error("tf2_net_poll_error: bad argument"); return TF2_ERR_ARG; }
   const WorkPlan* wp = nullptr;
-  {
+  auto ito = outputs_ws.find(ws);
+  if (ito != outputs_ws.end() && ito->second == batch) {
+    wp = plan(batch, PLAN_OUTPUTS);                         // the workspace's last step was a tf2_ssd_run
+  } else {
     const WorkPlan* a = plan(batch, false);
     auto itk = plans.find(std::make_pair(batch, 1));
     if (itk != plans.end() && ws_bytes >= itk->second.total_bytes) wp = &itk->second;

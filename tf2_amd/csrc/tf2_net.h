@@ -31,9 +31,12 @@ struct LayerExec {
   int out_off = 0;         // channel offset inside out_tensor (concat slice)
 };
 
+enum PlanMode { PLAN_ORDINARY = 0, PLAN_KEEP_ALL = 1, PLAN_OUTPUTS = 2 };   // Net::plan
+
 struct WorkPlan {
   int batch = 0;
   bool keep_all = false;
+  bool outputs_kept = false;   // PLAN_OUTPUTS: sink rows live to the end of the step, no direct logits store
   std::vector<TensorPlan> tensors;
   std::vector<LayerExec> exec;
   int input_tensor = -1;
@@ -168,7 +171,8 @@ struct Net {
   std::vector<int> out_Cp;               // channel padding of each layer's own output tensor
   std::vector<int> concat_C;             // channels of each concat tensor
 
-  std::map<std::pair<int, int>, WorkPlan> plans;   // (batch, keep_all) -> plan
+  std::map<std::pair<int, int>, WorkPlan> plans;   // (batch, PlanMode) -> plan
+  std::map<const void*, int> outputs_ws;           // workspace -> batch of its last step, where that step ran the outputs-kept plan
   std::list<LaunchPlan> launch_plans;              // prepared steps, keyed by (batch, plan, workspace, packed image); a list: growth and
                                                    // eviction never move a plan another thread is walking (oldest evicted at 64, under run_mutex)
   std::mutex run_mutex;                            // serialises run(): plan lookup / build, stream history, enqueue (tf2_amd.h threading note)
@@ -195,7 +199,8 @@ struct Net {
   const PackLayer* pack_layer_alt(int l) const;
   bool pair_candidate(int l) const;        // rows l and l + 1 are independent plain conv rows (one launch may compute both)
   uint64_t tables_hash() const;
-  const WorkPlan* plan(int batch, bool keep_all);
+  const WorkPlan* plan(int batch, int mode);       // mode: PlanMode (a bool keep_all reads as ORDINARY / KEEP_ALL)
+  bool is_sink(int l) const;
   const LaunchPlan* launch_plan(int batch, const WorkPlan* wp, void* ws, bool concurrent, bool allow_groups);
   size_t workspace_size(int batch, bool keep_all);      // plan(...)->total_bytes under the handle's mutex
   tf2_status describe_workspace(int batch, bool keep_all, std::vector<TensorPlan>* tensors, std::vector<LayerExec>* rows);
@@ -216,7 +221,8 @@ struct Net {
   size_t logits_bytes(int batch) const;
   tf2_status poll_error(int batch, void* ws, size_t ws_bytes, void* stream);
   tf2_status run(const void* images, bool images_are_q, int batch, void* ws, size_t ws_bytes,
-                 int8_t* logits, void* stream, int concurrency = -1, void* mark_event = nullptr, int mark_after_layer = -1);
+                 int8_t* logits, void* stream, int concurrency = -1, void* mark_event = nullptr, int mark_after_layer = -1,
+                 bool outputs_kept = false);
   int issue(const Launch& st, const LaunchPlan* lp, const void* images, bool images_are_q, int8_t* logits, void* stream);
   tf2_status describe_launches(int batch, bool concurrent, std::vector<std::pair<int, struct LaunchRecord>>* out);
   tf2_status read_layer(int layer, int batch, const void* ws, int8_t* dst, size_t cap, void* stream);
