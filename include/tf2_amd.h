@@ -279,6 +279,48 @@ tf2_status tf2_ssd_run(tf2_ssd* s, const void* images_dev, int images_are_q, int
 tf2_status tf2_ssd_detect(tf2_ssd* s, const float* boxes_dev, const float* scores_dev, int batch, void* scratch_dev,
                           size_t scratch_bytes, float* det_dev, int32_t* counts_dev, void* hip_stream);
 
+/* ---- Image preprocessing on the device (TransForm_Kit/Quantization/data_loader.py:26-83; INTEGRATION.md "Image preprocessing") ----
+ * uint8 pixels (HWC, 3 or 4 bytes a pixel, any row pitch) -> the net's input, float32 [batch][3][image_h][image_w] (what
+ * tf2_net_run reads) or, out_q = 1, int8 quantised with 2^-Q0 as runner.cpp:158-164 does (what tf2_net_run_q / images_are_q = 1
+ * read; the same bytes prep_input would make of the float output).  Per net channel c, output pixel (y, x) of image b, with
+ * Y = y + crop_y, X = x + crop_x:
+ *   fy = (Y + 0.5) * (h / resize_h) - 0.5 in double; y0 = floor(fy), wy = (float)(fy - y0); y0 < 0: y0 = 0, wy = 0;
+ *   y0 >= h - 1: y0 = h - 1, wy = 0; y1 = min(y0 + 1, h - 1); the same for columns (half-pixel centres, edge clamp, no antialiasing);
+ *   in float32, in this order: top = p00*(1-wx) + p01*wx, bot = p10*(1-wx) + p11*wx, r = top*(1-wy) + bot*wy (p: byte
+ *   src_channel[c] of the pixel); round_resized: r = clamp(rint(r), 0, 255); v = (r - mean[c]) * scale[c].
+ * tf2_amd.preprocess.reference is the host statement; the device output is bit-identical to it.
+ * Host checks (TF2_ERR_ARG with a message, before any device call): desc size, pixel_bytes 3 or 4, src_channel in
+ * 0..pixel_bytes-1, finite means and scales, round_resized 0 or 1, the net's image_c == 3, batch >= 1, non-null pointers, out_q = 1
+ * only once the q table is set (Q0 is read at call time).
+ * Device checks: the records are device data (refill them between graph replays), so the kernel validates each one and writes
+ * status_dev[b] = 0, or an OR of TF2_PREP_* bits; a malformed image's output is all zeros and none of its pixels is read.  No read
+ * leaves [pixels_dev, pixels_dev + pixels_bytes).  The grid depends only on batch and the net's image size: a captured graph
+ * stays valid for new images of new sizes.  Enqueued on hip_stream; no allocation, no synchronisation. */
+typedef struct tf2_image_src {      /* one per image, in DEVICE memory (refillable between graph replays) */
+  int64_t offset;                   /* byte offset of pixel (0,0) in the pixel buffer */
+  int32_t h, w, row_pitch;          /* source size, bytes between rows */
+  int32_t resize_h, resize_w;       /* size after resize (== h, w: none) */
+  int32_t crop_y, crop_x;           /* top-left of the image_h x image_w window in the resized image */
+  int32_t reserved;
+} tf2_image_src;
+typedef struct tf2_preprocess_desc {
+  uint32_t size;                    /* sizeof, as tf2_run_opts */
+  int32_t pixel_bytes;              /* 3 (RGB/BGR) or 4 (RGBA...) */
+  int32_t src_channel[3];           /* net channel c reads source byte src_channel[c] of a pixel */
+  int32_t round_resized;
+  float mean[3], scale[3];
+} tf2_preprocess_desc;
+enum {                              /* status_dev bits of a malformed record */
+  TF2_PREP_BAD_SIZE = 1,            /* h or w outside 1..32767 */
+  TF2_PREP_BAD_PITCH = 2,           /* row_pitch < w * pixel_bytes */
+  TF2_PREP_BAD_OFFSET = 4,          /* offset < 0 */
+  TF2_PREP_OUT_OF_BUFFER = 8,       /* offset + (h-1) * row_pitch + w * pixel_bytes > pixels_bytes (tested when bits 1, 2, 4 are clear) */
+  TF2_PREP_BAD_RESIZE = 16,         /* resize_h or resize_w outside 1..32767 */
+  TF2_PREP_BAD_CROP = 32            /* the image_h x image_w window at (crop_y, crop_x) leaves the resized image */
+};
+tf2_status tf2_preprocess(const tf2_net* net, const tf2_preprocess_desc* d, const uint8_t* pixels_dev, size_t pixels_bytes,
+                          const tf2_image_src* srcs_dev, int batch, int out_q, void* out_dev, int32_t* status_dev, void* stream);
+
 /* ---- Evaluation (network_helper.cpp:143-207): top-k with the reference's tie rule ---- */
 tf2_status tf2_topk(const int8_t* logits, const int8_t* q_last_row, int n, int k,
                     int32_t* labels, float* features);

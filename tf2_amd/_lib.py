@@ -62,6 +62,18 @@ class SsdDesc(C.Structure):
                 ("conf_row", C.c_int32 * 8), ("priors", C.c_void_p), ("n_priors", C.c_int32)]
 
 
+class ImageSrc(C.Structure):
+    """tf2_image_src (include/tf2_amd.h): one per image, in device memory."""
+    _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("row_pitch", C.c_int32), ("resize_h", C.c_int32),
+                ("resize_w", C.c_int32), ("crop_y", C.c_int32), ("crop_x", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PreprocessDesc(C.Structure):
+    """tf2_preprocess_desc (include/tf2_amd.h)."""
+    _fields_ = [("size", C.c_uint32), ("pixel_bytes", C.c_int32), ("src_channel", C.c_int32 * 3), ("round_resized", C.c_int32),
+                ("mean", C.c_float * 3), ("scale", C.c_float * 3)]
+
+
 class NetDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "n_layers", "n_conv", "n_q_rows", "max_out_channel", "image_c", "image_h", "image_w",
@@ -153,6 +165,7 @@ def lib() -> C.CDLL:
     L.tf2_ssd_detect_scratch_size.restype = sz
     L.tf2_ssd_run.argtypes = [vp, vp, C.c_int, C.c_int, vp, sz, vp, vp, vp, vp, vp, vp, vp]
     L.tf2_ssd_detect.argtypes = [vp, vp, vp, C.c_int, vp, sz, vp, vp, vp]
+    L.tf2_preprocess.argtypes = [vp, C.POINTER(PreprocessDesc), vp, sz, vp, C.c_int, C.c_int, vp, vp, vp]
     _lib = L
     return L
 
@@ -163,7 +176,8 @@ EXPORTED = [
     "tf2_net_get_bias_bn", "tf2_net_pack", "tf2_net_packed_size", "tf2_net_packed_copy",
     "tf2_net_packed_adopt", "tf2_net_bind_device", "tf2_net_workspace_size", "tf2_net_logits_size", "tf2_net_reload_options", "tf2_net_run",
     "tf2_net_run_q", "tf2_net_run_ex", "tf2_net_run_stats", "tf2_net_poll_error", "tf2_net_describe_launches", "tf2_net_describe_workspace", "tf2_net_read_layer", "tf2_net_profile", "tf2_net_profile_read", "tf2_net_profile_loop_read", "tf2_topk",
-    "tf2_ssd_create", "tf2_ssd_destroy", "tf2_ssd_workspace_size", "tf2_ssd_detect_scratch_size", "tf2_ssd_run", "tf2_ssd_detect"]
+    "tf2_ssd_create", "tf2_ssd_destroy", "tf2_ssd_workspace_size", "tf2_ssd_detect_scratch_size", "tf2_ssd_run", "tf2_ssd_detect",
+    "tf2_preprocess"]
 
 
 def parse_opts(text: str) -> dict:

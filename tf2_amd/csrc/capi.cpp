@@ -5,6 +5,7 @@
 #include "tf2_device.h"
 #include "opts.h"
 #include "ssd_detect.h"
+#include "preprocess.h"
 
 using namespace tf2;
 
@@ -290,6 +291,12 @@ tf2_status tf2_ssd_detect(tf2_ssd* s, const float* boxes_dev, const float* score
                           float* det_dev, int32_t* counts_dev, void* hip_stream) {
   if (!s) { set_error("null tf2_ssd handle"); return TF2_ERR_ARG; }
   return s->impl.detect(boxes_dev, scores_dev, batch, scratch, scratch_bytes, det_dev, counts_dev, hip_stream);
+}
+
+tf2_status tf2_preprocess(const tf2_net* net, const tf2_preprocess_desc* d, const uint8_t* pixels_dev, size_t pixels_bytes,
+                          const tf2_image_src* srcs_dev, int batch, int out_q, void* out_dev, int32_t* status_dev, void* stream) {
+  CHECK_NET(net);
+  return preprocess(net->impl, d, pixels_dev, pixels_bytes, srcs_dev, batch, out_q, out_dev, status_dev, stream);
 }
 
 tf2_status tf2_net_read_layer(tf2_net* net, int layer, int batch, const void* ws, int8_t* host_dst,
