@@ -321,6 +321,41 @@ enum {                              /* status_dev bits of a malformed record */
 tf2_status tf2_preprocess(const tf2_net* net, const tf2_preprocess_desc* d, const uint8_t* pixels_dev, size_t pixels_bytes,
                           const tf2_image_src* srcs_dev, int batch, int out_q, void* out_dev, int32_t* status_dev, void* stream);
 
+/* ---- Classification on the device (Evaluation, network_helper.cpp:143-207; INTEGRATION.md "Classification on the device") ----
+ * A classifier belongs to a network handle whose final map is 1 x 1 (it reads the handle's q table at create: a later set_q needs
+ * a new classifier).  Per image, from the int8 logits [batch][n] a run writes (n = N of the last row) and the runtime Q row of the
+ * last layer's output -- the row Evaluation's callers pass, q[NUM_LAYER] (main.cpp:53):
+ *   features   f[i] = (float)logit[i] / (float)(1 << sh[i]), sh[i] = -q[i] in 0..30 (exact in float32);
+ *   top-k      the first top_k entries by (feature descending, index descending on equal features) -- the closed form of the
+ *              reference's k bubble passes with a strict '>'; labels and features are bit-identical to the host function at the
+ *              end of this header;
+ *   probs      max-subtracted float32 softmax: d[i] = f[i] - fmax (one IEEE subtraction), p[i] = expf(d[i]) / sum_j expf(d[j]),
+ *              the sum in a fixed order (64 strided partial sums, then a 6-step butterfly), so a run repeats bit for bit.  The
+ *              reference's text (and network.Evaluation, which keeps it) does not subtract the maximum: its exp overflows once a
+ *              feature passes ~88 and the result is inf / inf.  Mathematically the two agree; where Evaluation's result is finite
+ *              the two differ by rounding only;
+ *   truth      truth[b] < 0: unlabelled, rank[b] = -1, nothing counted; 0 <= truth[b] < n: rank[b] = the label's position among
+ *              the top_k (0 = best) or -1; truth[b] >= n: a bad label, rank[b] = -1;
+ *   tally      uint64 [4], ACCUMULATED (the caller zeroes it): {images with truth >= 0 (bad labels included: they are misses),
+ *              rank == 0, rank >= 0, bad labels}.  Integer adds only: exact, order-independent, and a captured graph replayed
+ *              over a validation set leaves the counts on the device with no synchronisation in between.
+ * tf2_amd.classify.reference is the host statement.  Create checks on the host, before any device call (TF2_ERR_ARG with a
+ * message; TF2_ERR_STATE before the q table is set): desc size, a 1 x 1 final map that is the net's only output (SSD300 has heads: refused), top_k in 1..min(n, 64), every Q of the last row
+ * in 0..30; n outside 2..4096 is TF2_ERR_UNSUPPORTED.  The handle holds read-only device constants (the 2^-sh scales).  A run
+ * checks batch >= 1 and non-null logits_dev / labels_dev, then enqueues one kernel on hip_stream: no allocation, no
+ * synchronisation, a grid that depends on batch alone (graph-capturable; several streams run side by side on their own outputs).
+ * labels_dev int32 [batch][top_k]; every later pointer is optional (NULL): features_dev, probs_dev float32 [batch][top_k],
+ * all_probs_dev float32 [batch][n], truth_dev int32 [batch], rank_dev int32 [batch], tally_dev uint64 [4]. */
+typedef struct tf2_cls tf2_cls;
+typedef struct tf2_cls_desc {
+  uint32_t size;                    /* sizeof(tf2_cls_desc) */
+  int32_t top_k;                    /* 1..min(n, 64) */
+} tf2_cls_desc;
+tf2_status tf2_cls_create(tf2_net* net, const tf2_cls_desc* d, tf2_cls** out);
+void       tf2_cls_destroy(tf2_cls* c);
+tf2_status tf2_cls_run(tf2_cls* c, const int8_t* logits_dev, int batch, int32_t* labels_dev, float* features_dev, float* probs_dev,
+                       float* all_probs_dev, const int32_t* truth_dev, int32_t* rank_dev, uint64_t* tally_dev, void* hip_stream);
+
 /* ---- Evaluation (network_helper.cpp:143-207): top-k with the reference's tie rule ---- */
 tf2_status tf2_topk(const int8_t* logits, const int8_t* q_last_row, int n, int k,
                     int32_t* labels, float* features);

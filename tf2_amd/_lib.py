@@ -74,6 +74,11 @@ class PreprocessDesc(C.Structure):
                 ("mean", C.c_float * 3), ("scale", C.c_float * 3)]
 
 
+class ClsDesc(C.Structure):
+    """tf2_cls_desc (include/tf2_amd.h)."""
+    _fields_ = [("size", C.c_uint32), ("top_k", C.c_int32)]
+
+
 class NetDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "n_layers", "n_conv", "n_q_rows", "max_out_channel", "image_c", "image_h", "image_w",
@@ -166,6 +171,10 @@ def lib() -> C.CDLL:
     L.tf2_ssd_run.argtypes = [vp, vp, C.c_int, C.c_int, vp, sz, vp, vp, vp, vp, vp, vp, vp]
     L.tf2_ssd_detect.argtypes = [vp, vp, vp, C.c_int, vp, sz, vp, vp, vp]
     L.tf2_preprocess.argtypes = [vp, C.POINTER(PreprocessDesc), vp, sz, vp, C.c_int, C.c_int, vp, vp, vp]
+    L.tf2_cls_create.argtypes = [vp, C.POINTER(ClsDesc), C.POINTER(vp)]
+    L.tf2_cls_destroy.argtypes = [vp]
+    L.tf2_cls_destroy.restype = None
+    L.tf2_cls_run.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -177,7 +186,7 @@ EXPORTED = [
     "tf2_net_packed_adopt", "tf2_net_bind_device", "tf2_net_workspace_size", "tf2_net_logits_size", "tf2_net_reload_options", "tf2_net_run",
     "tf2_net_run_q", "tf2_net_run_ex", "tf2_net_run_stats", "tf2_net_poll_error", "tf2_net_describe_launches", "tf2_net_describe_workspace", "tf2_net_read_layer", "tf2_net_profile", "tf2_net_profile_read", "tf2_net_profile_loop_read", "tf2_topk",
     "tf2_ssd_create", "tf2_ssd_destroy", "tf2_ssd_workspace_size", "tf2_ssd_detect_scratch_size", "tf2_ssd_run", "tf2_ssd_detect",
-    "tf2_preprocess"]
+    "tf2_preprocess", "tf2_cls_create", "tf2_cls_destroy", "tf2_cls_run"]
 
 
 def parse_opts(text: str) -> dict:

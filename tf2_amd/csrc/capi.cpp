@@ -6,11 +6,13 @@
 #include "opts.h"
 #include "ssd_detect.h"
 #include "preprocess.h"
+#include "classify.h"
 
 using namespace tf2;
 
 struct tf2_net { Net impl; };
 struct tf2_ssd { SsdDetector impl; };
+struct tf2_cls { Classifier impl; };
 
 #define CHECK_NET(n)                                              \
   if (!(n)) { set_error("null tf2_net handle"); return TF2_ERR_ARG; }
@@ -297,6 +299,27 @@ tf2_status tf2_preprocess(const tf2_net* net, const tf2_preprocess_desc* d, cons
                           const tf2_image_src* srcs_dev, int batch, int out_q, void* out_dev, int32_t* status_dev, void* stream) {
   CHECK_NET(net);
   return preprocess(net->impl, d, pixels_dev, pixels_bytes, srcs_dev, batch, out_q, out_dev, status_dev, stream);
+}
+
+tf2_status tf2_cls_create(tf2_net* net, const tf2_cls_desc* d, tf2_cls** out) {
+  CHECK_NET(net);
+  if (!out) { set_error("tf2_cls_create: null argument"); return TF2_ERR_ARG; }
+  tf2_cls* c = new (std::nothrow) tf2_cls();
+  if (!c) { set_error("out of memory"); return TF2_ERR_SIZE; }
+  const tf2_status st = c->impl.create(&net->impl, d);
+  if (st != TF2_OK) { delete c; return st; }
+  *out = c;
+  return TF2_OK;
+}
+
+void tf2_cls_destroy(tf2_cls* c) { delete c; }
+
+tf2_status tf2_cls_run(tf2_cls* c, const int8_t* logits_dev, int batch, int32_t* labels_dev, float* features_dev, float* probs_dev,
+                       float* all_probs_dev, const int32_t* truth_dev, int32_t* rank_dev, uint64_t* tally_dev, void* stream) {
+  if (batch < 1) { set_error("tf2_cls_run: batch must be >= 1"); return TF2_ERR_ARG; }
+  if (!logits_dev || !labels_dev) { set_error("tf2_cls_run: null logits_dev / labels_dev"); return TF2_ERR_ARG; }
+  if (!c) { set_error("null tf2_cls handle"); return TF2_ERR_ARG; }
+  return c->impl.run(logits_dev, batch, labels_dev, features_dev, probs_dev, all_probs_dev, truth_dev, rank_dev, tally_dev, stream);
 }
 
 tf2_status tf2_net_read_layer(tf2_net* net, int layer, int batch, const void* ws, int8_t* host_dst,
