@@ -356,6 +356,80 @@ void       tf2_cls_destroy(tf2_cls* c);
 tf2_status tf2_cls_run(tf2_cls* c, const int8_t* logits_dev, int batch, int32_t* labels_dev, float* features_dev, float* probs_dev,
                        float* all_probs_dev, const int32_t* truth_dev, int32_t* rank_dev, uint64_t* tally_dev, void* hip_stream);
 
+/* ---- Detection accuracy on the device (the PASCAL VOC devkit protocol behind the README's SSD mAP; INTEGRATION.md "Detection accuracy
+ * on the device") ----
+ * The reference ships no evaluation code (ssd.py: no weights, no dataset, no eval script), so this statement is the canonical one.
+ * An evaluator belongs to no net and holds no device memory: it takes any det [batch][num_classes][top_k][5] / counts
+ * [batch][num_classes] of the layout tf2_ssd_run writes, ground truth in the same normalised corner form, and keeps the dataset-level
+ * record in a caller-owned device buffer, the STORE, of `capacity` image slots.
+ * Matching (tf2_det_eval_run, one kernel a step): per image and class c >= 1, walk the class's rows r = 0 .. counts-1 (best first).
+ * For row r go over the image's ground truths of class c in index order, difficult ones included, and keep the one with the largest
+ * IoU (strict '>' starting from none: the lowest index wins a tie, a NaN IoU never wins).  Then flag[r] =
+ *    0  no winner, or its IoU is not > iou_thresh (strict, float32): false positive
+ *   -1  the winner is difficult: ignored
+ *    1  the winner is not yet taken: true positive, and it is now taken
+ *    0  the winner is already taken: duplicate (no fall-back to the second best, as in the devkit)
+ *   -2  rows past counts[b][c], and every row of class 0.
+ * IoU is plain IoU on the caller's coordinates in IEEE float32, ssd._iou_one_to_many's arithmetic inter / ((area_gt - inter) +
+ * area_det) with the min / max of ssd_detect.hip (a NaN operand is ignored); the devkit's "+1 pixel" convention is not applied.
+ * ssd.match_reference is the host statement; the device output is bit-identical to it.
+ * Store layout (tf2_det_eval_store_size bytes; sections in this order, no padding, K = top_k, C = num_classes):
+ *   seen   int32   [capacity]          1 once an image was evaluated into the slot
+ *   npos   int32   [capacity][C]       non-difficult ground truths per class
+ *   scores float32 [capacity][C][K]    the rows' scores (0 where the flag is -2)
+ *   flags  int8    [capacity][C][K]
+ * A step writes every byte of each slot it owns (slot_dev[b]) with ordinary stores: no atomics, no append counters.  The store is a
+ * pure function of the set of (slot, image) pairs: independent of replay order and streams; evaluating an image twice overwrites;
+ * slots need no clearing between epochs, only `seen` is zeroed (tf2_det_eval_store_init: a memset on the stream).  The slots of one
+ * step, and of steps in flight side by side, must be distinct.  slot_dev[b] < 0: the image is skipped (padding of a last batch),
+ * nothing is written to the store and status_dev[b] = 0.
+ * Device checks: the records are device data (refill them between graph replays, like tf2_image_src), so the kernel validates each
+ * image before it uses anything as an index and writes status_dev[b] = 0 or an OR of TF2_EVAL_* bits; a malformed image writes
+ * nothing to the store and its `seen` is not set.  No read leaves the buffers described here.  Optional flags_out_dev
+ * [batch][C][K] int8 receives the step's flags directly (-2 everywhere for a skipped or malformed image).
+ * Host checks (TF2_ERR_ARG with a message, before any device call): create -- desc size, num_classes 2..256, top_k 1..256, max_gt
+ * 1..256, capacity >= 1, iou_thresh finite and >= 0; run -- batch >= 1, non-null det / counts / gt / gt_count / slot / store / status,
+ * store_bytes >= tf2_det_eval_store_size.  The grid depends on batch and the handle's constants alone; no allocation, no
+ * synchronisation (graph-capturable).
+ * tf2_det_eval_summarise runs on the HOST CPU on a host copy of the store, once per dataset: per class the records of seen slots with
+ * flag >= 0, ordered by (score descending, slot ascending, rank ascending; a NaN score last) -- the devkit's argsort leaves ties
+ * undefined -- then cumulative tp / fp (int64), recall = tp / npos, precision = tp / (tp + fp) in double, and AP by the devkit's
+ * 11-point metric (use_07_metric != 0: thresholds k * 0.1, k = 0..10, the maximum precision at recall >= threshold or 0) or its
+ * all-point metric (recall bracketed by 0 and 1, the monotone precision envelope from the right, sum of delta recall x precision).
+ * per_class [C]; a class with npos == 0 (class 0 always) has ap = NaN and is left out of *map, the mean over the others (NaN if
+ * there is none); *images = number of seen slots. */
+typedef struct tf2_det_eval tf2_det_eval;
+typedef struct tf2_gt_box {         /* one ground truth, in DEVICE memory, [batch][max_gt] */
+  float x1, y1, x2, y2;
+  int32_t label;                    /* 1..num_classes-1 */
+  int32_t difficult;                /* != 0: matched detections are ignored, not counted in npos */
+} tf2_gt_box;
+typedef struct tf2_det_eval_desc {
+  uint32_t size;                    /* sizeof(tf2_det_eval_desc) */
+  int32_t num_classes;              /* 2..256, including background class 0 */
+  int32_t top_k;                    /* 1..256 */
+  int32_t max_gt;                   /* 1..256: ground truths an image may have */
+  int32_t capacity;                 /* >= 1: image slots of the store */
+  float iou_thresh;                 /* finite, >= 0 (VOC: 0.5) */
+} tf2_det_eval_desc;
+enum {                              /* status_dev bits of a malformed image */
+  TF2_EVAL_BAD_SLOT = 1,            /* slot >= capacity */
+  TF2_EVAL_BAD_COUNT = 2,           /* gt_count outside 0..max_gt (labels and boxes are then not looked at) */
+  TF2_EVAL_BAD_LABEL = 4,           /* a label outside 1..num_classes-1 */
+  TF2_EVAL_BAD_BOX = 8,             /* a non-finite coordinate, or x2 < x1, or y2 < y1 */
+  TF2_EVAL_BAD_DET = 16             /* a counts[b][c] outside 0..top_k */
+};
+typedef struct tf2_det_eval_class { double ap; int64_t npos, tp, fp; } tf2_det_eval_class;
+tf2_status tf2_det_eval_create(const tf2_det_eval_desc* d, tf2_det_eval** out);
+void       tf2_det_eval_destroy(tf2_det_eval* e);
+size_t     tf2_det_eval_store_size(const tf2_det_eval* e);
+tf2_status tf2_det_eval_store_init(const tf2_det_eval* e, void* store_dev, size_t store_bytes, void* hip_stream);
+tf2_status tf2_det_eval_run(const tf2_det_eval* e, const float* det_dev, const int32_t* counts_dev, const tf2_gt_box* gt_dev,
+                            const int32_t* gt_count_dev, const int32_t* slot_dev, int batch, void* store_dev, size_t store_bytes,
+                            int32_t* status_dev, int8_t* flags_out_dev, void* hip_stream);
+tf2_status tf2_det_eval_summarise(const tf2_det_eval* e, const void* store_host, size_t store_bytes, int use_07_metric,
+                                  tf2_det_eval_class* per_class, int64_t* images, double* map);
+
 /* ---- Evaluation (network_helper.cpp:143-207): top-k with the reference's tie rule ---- */
 tf2_status tf2_topk(const int8_t* logits, const int8_t* q_last_row, int n, int k,
                     int32_t* labels, float* features);

@@ -79,6 +79,17 @@ class ClsDesc(C.Structure):
     _fields_ = [("size", C.c_uint32), ("top_k", C.c_int32)]
 
 
+class DetEvalDesc(C.Structure):
+    """tf2_det_eval_desc (include/tf2_amd.h)."""
+    _fields_ = [("size", C.c_uint32), ("num_classes", C.c_int32), ("top_k", C.c_int32), ("max_gt", C.c_int32),
+                ("capacity", C.c_int32), ("iou_thresh", C.c_float)]
+
+
+class DetEvalClass(C.Structure):
+    """tf2_det_eval_class (include/tf2_amd.h)."""
+    _fields_ = [("ap", C.c_double), ("npos", C.c_int64), ("tp", C.c_int64), ("fp", C.c_int64)]
+
+
 class NetDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "n_layers", "n_conv", "n_q_rows", "max_out_channel", "image_c", "image_h", "image_w",
@@ -175,6 +186,14 @@ def lib() -> C.CDLL:
     L.tf2_cls_destroy.argtypes = [vp]
     L.tf2_cls_destroy.restype = None
     L.tf2_cls_run.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tf2_det_eval_create.argtypes = [C.POINTER(DetEvalDesc), C.POINTER(vp)]
+    L.tf2_det_eval_destroy.argtypes = [vp]
+    L.tf2_det_eval_destroy.restype = None
+    L.tf2_det_eval_store_size.argtypes = [vp]
+    L.tf2_det_eval_store_size.restype = sz
+    L.tf2_det_eval_store_init.argtypes = [vp, vp, sz, vp]
+    L.tf2_det_eval_run.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, sz, vp, vp, vp]
+    L.tf2_det_eval_summarise.argtypes = [vp, vp, sz, C.c_int, C.POINTER(DetEvalClass), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -186,7 +205,9 @@ EXPORTED = [
     "tf2_net_packed_adopt", "tf2_net_bind_device", "tf2_net_workspace_size", "tf2_net_logits_size", "tf2_net_reload_options", "tf2_net_run",
     "tf2_net_run_q", "tf2_net_run_ex", "tf2_net_run_stats", "tf2_net_poll_error", "tf2_net_describe_launches", "tf2_net_describe_workspace", "tf2_net_read_layer", "tf2_net_profile", "tf2_net_profile_read", "tf2_net_profile_loop_read", "tf2_topk",
     "tf2_ssd_create", "tf2_ssd_destroy", "tf2_ssd_workspace_size", "tf2_ssd_detect_scratch_size", "tf2_ssd_run", "tf2_ssd_detect",
-    "tf2_preprocess", "tf2_cls_create", "tf2_cls_destroy", "tf2_cls_run"]
+    "tf2_preprocess", "tf2_cls_create", "tf2_cls_destroy", "tf2_cls_run",
+    "tf2_det_eval_create", "tf2_det_eval_destroy", "tf2_det_eval_store_size", "tf2_det_eval_store_init", "tf2_det_eval_run",
+    "tf2_det_eval_summarise"]
 
 
 def parse_opts(text: str) -> dict:

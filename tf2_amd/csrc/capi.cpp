@@ -7,12 +7,14 @@
 #include "ssd_detect.h"
 #include "preprocess.h"
 #include "classify.h"
+#include "ssd_eval.h"
 
 using namespace tf2;
 
 struct tf2_net { Net impl; };
 struct tf2_ssd { SsdDetector impl; };
 struct tf2_cls { Classifier impl; };
+struct tf2_det_eval { DetEvaluator impl; };
 
 #define CHECK_NET(n)                                              \
   if (!(n)) { set_error("null tf2_net handle"); return TF2_ERR_ARG; }
@@ -320,6 +322,42 @@ tf2_status tf2_cls_run(tf2_cls* c, const int8_t* logits_dev, int batch, int32_t*
   if (!logits_dev || !labels_dev) { set_error("tf2_cls_run: null logits_dev / labels_dev"); return TF2_ERR_ARG; }
   if (!c) { set_error("null tf2_cls handle"); return TF2_ERR_ARG; }
   return c->impl.run(logits_dev, batch, labels_dev, features_dev, probs_dev, all_probs_dev, truth_dev, rank_dev, tally_dev, stream);
+}
+
+tf2_status tf2_det_eval_create(const tf2_det_eval_desc* d, tf2_det_eval** out) {
+  if (!out) { set_error("tf2_det_eval_create: null argument"); return TF2_ERR_ARG; }
+  tf2_det_eval* e = new (std::nothrow) tf2_det_eval();
+  if (!e) { set_error("out of memory"); return TF2_ERR_SIZE; }
+  const tf2_status st = e->impl.create(d);
+  if (st != TF2_OK) { delete e; return st; }
+  *out = e;
+  return TF2_OK;
+}
+
+void tf2_det_eval_destroy(tf2_det_eval* e) { delete e; }
+
+size_t tf2_det_eval_store_size(const tf2_det_eval* e) { return e ? e->impl.store_size() : 0; }
+
+tf2_status tf2_det_eval_store_init(const tf2_det_eval* e, void* store_dev, size_t store_bytes, void* hip_stream) {
+  if (!e) { set_error("null tf2_det_eval handle"); return TF2_ERR_ARG; }
+  return e->impl.store_init(store_dev, store_bytes, hip_stream);
+}
+
+tf2_status tf2_det_eval_run(const tf2_det_eval* e, const float* det_dev, const int32_t* counts_dev, const tf2_gt_box* gt_dev,
+                            const int32_t* gt_count_dev, const int32_t* slot_dev, int batch, void* store_dev, size_t store_bytes,
+                            int32_t* status_dev, int8_t* flags_out_dev, void* hip_stream) {
+  if (batch < 1) { set_error("tf2_det_eval_run: batch must be >= 1"); return TF2_ERR_ARG; }
+  if (!det_dev || !counts_dev) { set_error("tf2_det_eval_run: null det_dev / counts_dev"); return TF2_ERR_ARG; }
+  if (!gt_dev || !gt_count_dev || !slot_dev) { set_error("tf2_det_eval_run: null gt_dev / gt_count_dev / slot_dev"); return TF2_ERR_ARG; }
+  if (!store_dev || !status_dev) { set_error("tf2_det_eval_run: null store_dev / status_dev"); return TF2_ERR_ARG; }
+  if (!e) { set_error("null tf2_det_eval handle"); return TF2_ERR_ARG; }
+  return e->impl.run(det_dev, counts_dev, gt_dev, gt_count_dev, slot_dev, batch, store_dev, store_bytes, status_dev, flags_out_dev, hip_stream);
+}
+
+tf2_status tf2_det_eval_summarise(const tf2_det_eval* e, const void* store_host, size_t store_bytes, int use_07_metric,
+                                  tf2_det_eval_class* per_class, int64_t* images, double* map) {
+  if (!e) { set_error("null tf2_det_eval handle"); return TF2_ERR_ARG; }
+  return e->impl.summarise(store_host, store_bytes, use_07_metric, per_class, images, map);
 }
 
 tf2_status tf2_net_read_layer(tf2_net* net, int layer, int batch, const void* ws, int8_t* host_dst,

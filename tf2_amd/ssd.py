@@ -304,3 +304,325 @@ class DeviceDetector:
         ws = self._ws[batch]
         stream = stream or torch.cuda.current_stream(self.net.device)
         _lib.check(_lib.lib().tf2_net_poll_error(self.net._h, batch, ws.data_ptr(), ws.numel(), stream.cuda_stream))
+
+
+# ---- detection accuracy: ground-truth matching and VOC mAP (tf2_det_eval_*, include/tf2_amd.h; csrc/ssd_eval.hip) ----------------
+# The reference ships no evaluation code, so the statement below is the canonical one: the PASCAL VOC devkit protocol behind the
+# README's mAP, with plain IoU on normalised coordinates (no "+1 pixel") and the devkit's undefined tie order pinned.
+
+GT_DTYPE = np.dtype([("box", np.float32, 4), ("label", np.int32), ("difficult", np.int32)])       # tf2_gt_box, 24 bytes
+EVAL_BAD_SLOT, EVAL_BAD_COUNT, EVAL_BAD_LABEL, EVAL_BAD_BOX, EVAL_BAD_DET = 1, 2, 4, 8, 16       # TF2_EVAL_*
+
+
+def pack_ground_truth(per_image, max_gt: int):
+    """Per-image ground truth -> the padded records of tf2_det_eval_run: (gt [B, max_gt] of GT_DTYPE, gt_count [B] int32).  An image
+    is an array [n, 6] of rows (x1, y1, x2, y2, label, difficult) in the normalised corner form of `det` (or a GT_DTYPE array [n]);
+    n = 0 is an image without objects."""
+    gt = np.zeros((len(per_image), max_gt), GT_DTYPE)
+    cnt = np.zeros(len(per_image), np.int32)
+    for b, rows in enumerate(per_image):
+        rows = np.asarray(rows)
+        if rows.dtype != GT_DTYPE:
+            rows = rows.reshape(-1, 6)
+            rec = np.zeros(rows.shape[0], GT_DTYPE)
+            rec["box"], rec["label"], rec["difficult"] = rows[:, :4], rows[:, 4], rows[:, 5]
+            rows = rec
+        if rows.shape[0] > max_gt:
+            raise ValueError(f"image {b} has {rows.shape[0]} ground truths, max_gt is {max_gt}")
+        gt[b, :rows.shape[0]] = rows
+        cnt[b] = rows.shape[0]
+    return gt, cnt
+
+
+def _gt_records(gt):
+    """GT_DTYPE view [B, max_gt] of ground-truth records given as such, or as their int32 words [B, max_gt, 6] (numpy / torch)"""
+    if hasattr(gt, "detach"):
+        gt = gt.detach().cpu().numpy()
+    gt = np.ascontiguousarray(gt)
+    return gt if gt.dtype == GT_DTYPE else gt.view(GT_DTYPE).reshape(gt.shape[0], gt.shape[1])
+
+
+def _host(a, dtype):
+    return np.ascontiguousarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype)
+
+
+class MatchResult:
+    """flags int8 [B, C, K], scores float32 [B, C, K], npos int32 [B, C], status int32 [B]; duplicates int32 [B, C]: the rows among
+    the flag-0 ones whose winner passed the threshold but was taken (what the device does not record: for tests' censuses)"""
+
+    def __init__(self, flags, scores, npos, status, duplicates):
+        self.flags, self.scores, self.npos, self.status, self.duplicates = flags, scores, npos, status, duplicates
+
+
+def match_reference(det, counts, gt, gt_count, iou_thresh: float = 0.5, slots=None, capacity=None) -> MatchResult:
+    """The host statement of tf2_det_eval_run's kernel, its yardstick, per image: det [B, C, K, 5] rows (score, x1, y1, x2, y2) best
+    first, counts [B, C], gt [B, max_gt] records (pack_ground_truth), gt_count [B].  Per image and class c >= 1, for row r = 0 ..
+    counts-1: among the image's ground truths of class c in index order (difficult ones included) the one with the largest IoU,
+    strict '>' from none (the lowest index wins a tie, a NaN IoU never wins); flag 0 if there is none or its IoU is not >
+    iou_thresh (float32, strict), -1 if it is difficult, 1 if it is not yet taken (it is taken now), 0 if it is (a duplicate: no
+    fall-back to the second best).  Rows past counts and all of class 0: flag -2, score 0.  npos[b, c] = non-difficult ground truths.
+    IoU is _iou_one_to_many's float32 arithmetic, inter / ((area_gt - inter) + area_det), with the device's min / max (a NaN operand
+    is ignored: np.fmax / np.fmin; the same values for every non-NaN box).
+    status[b] is 0 or an OR of EVAL_BAD_*: gt_count outside 0..max_gt (labels and boxes are then not looked at), a label outside
+    1..C-1, a non-finite or inverted box, a count outside 0..K, and, with `slots` / `capacity`, a slot >= capacity; slot < 0 skips the
+    image (status 0).  A skipped or malformed image has flag -2 everywhere, scores and npos 0."""
+    det, counts = _host(det, np.float32), _host(counts, np.int32)
+    gt, gt_count = _gt_records(gt), _host(gt_count, np.int32)
+    B, C, K = det.shape[:3]
+    max_gt = gt.shape[1]
+    thr = np.float32(iou_thresh)
+    flags = np.full((B, C, K), -2, np.int8)
+    scores = np.zeros((B, C, K), np.float32)
+    npos = np.zeros((B, C), np.int32)
+    status = np.zeros(B, np.int32)
+    duplicates = np.zeros((B, C), np.int32)
+    for b in range(B):
+        if slots is not None:
+            if int(slots[b]) < 0:
+                continue
+            if capacity is not None and int(slots[b]) >= capacity:
+                status[b] |= EVAL_BAD_SLOT
+        n_gt = int(gt_count[b])
+        if n_gt < 0 or n_gt > max_gt:
+            status[b] |= EVAL_BAD_COUNT
+            n_gt = 0
+        g = gt[b, :n_gt]
+        box, label, difficult = g["box"], g["label"], g["difficult"] != 0
+        if ((label < 1) | (label >= C)).any():
+            status[b] |= EVAL_BAD_LABEL
+        if (~np.isfinite(box).all(axis=1) | (box[:, 2] < box[:, 0]) | (box[:, 3] < box[:, 1])).any():
+            status[b] |= EVAL_BAD_BOX
+        if ((counts[b] < 0) | (counts[b] > K)).any():
+            status[b] |= EVAL_BAD_DET
+        if status[b]:
+            continue
+        area_gt = (box[:, 2] - box[:, 0]) * (box[:, 3] - box[:, 1])
+        for c in range(1, C):
+            n = int(counts[b, c])
+            of_c = np.flatnonzero(label == c)
+            npos[b, c] = int((~difficult[of_c]).sum())
+            flags[b, c, :n] = 0
+            scores[b, c, :n] = det[b, c, :n, 0]
+            if n == 0 or of_c.size == 0:
+                continue
+            d = det[b, c, :n, 1:]
+            area_det = (d[:, 2] - d[:, 0]) * (d[:, 3] - d[:, 1])
+            gb = box[of_c]
+            lo_x, lo_y = np.fmax(gb[None, :, 0], d[:, None, 0]), np.fmax(gb[None, :, 1], d[:, None, 1])
+            hi_x, hi_y = np.fmin(gb[None, :, 2], d[:, None, 2]), np.fmin(gb[None, :, 3], d[:, None, 3])
+            with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+                inter = np.fmax(hi_x - lo_x, np.float32(0)) * np.fmax(hi_y - lo_y, np.float32(0))
+                iou = inter / ((area_gt[of_c][None, :] - inter) + area_det[:, None])          # [rows, ground truths of c]
+            assert iou.dtype == np.float32
+            iou = np.where(np.isnan(iou), -np.inf, iou)
+            win = iou.argmax(axis=1)                                                          # the first of the largest
+            best = iou[np.arange(n), win]
+            taken = np.zeros(of_c.size, bool)
+            for r in range(n):
+                if not best[r] > thr:
+                    continue
+                w = win[r]
+                if difficult[of_c[w]]:
+                    flags[b, c, r] = -1
+                elif not taken[w]:
+                    flags[b, c, r] = 1
+                    taken[w] = True
+                else:
+                    duplicates[b, c] += 1
+    return MatchResult(flags, scores, npos, status, duplicates)
+
+
+def voc_ap(rec, prec, use_07_metric: bool = False) -> float:
+    """The devkit's voc_ap: the 11-point metric (maximum precision at recall >= k * 0.1, k = 0..10, 0 where there is none, their
+    mean) or the all-point one (recall bracketed by 0 and 1, the monotone precision envelope from the right, sum of delta recall x
+    precision), in float64."""
+    rec, prec = np.asarray(rec, np.float64), np.asarray(prec, np.float64)
+    if use_07_metric:
+        ap = 0.0
+        for k in range(11):
+            t = k * 0.1
+            p = float(prec[rec >= t].max()) if (rec >= t).any() else 0.0
+            ap += p / 11.0
+        return ap
+    mrec = np.concatenate(([0.0], rec, [1.0]))
+    mpre = np.concatenate(([0.0], prec, [0.0]))
+    for i in range(mpre.size - 1, 0, -1):
+        mpre[i - 1] = max(mpre[i - 1], mpre[i])
+    i = np.flatnonzero(mrec[1:] != mrec[:-1])
+    return float(((mrec[i + 1] - mrec[i]) * mpre[i + 1]).sum())
+
+
+def voc_eval_reference(det, counts, gt, gt_count, image_ids=None, iou_thresh: float = 0.5, use_07_metric: bool = False) -> dict:
+    """The same protocol written independently of match_reference, in the devkit's global form (voc_eval): per class, every image's
+    detections in ONE list, sorted by (score descending, image id ascending, rank ascending -- the pinned order), walked once with
+    per-image taken flags, then voc_ap.  Within one image the global order restricted to that image is the row order (rows are best
+    first and ties keep the rank order), so per-image matching is the same protocol; tests/test_ssd_eval.py shows the two agree.
+    image_ids [B]: the images' positions in the dataset (the evaluator's slots; default 0..B-1), ids < 0 are left out.
+    Returns dict(ap [C] (NaN where npos == 0), npos, tp, fp [C], images, map: the mean AP over classes with npos > 0)."""
+    det, counts = _host(det, np.float32), _host(counts, np.int32)
+    gt, gt_count = _gt_records(gt), _host(gt_count, np.int32)
+    B, C, K = det.shape[:3]
+    ids = np.arange(B) if image_ids is None else np.asarray(image_ids, np.int64)
+    thr = np.float32(iou_thresh)
+    ap = np.full(C, np.nan)
+    npos, tps, fps = np.zeros(C, np.int64), np.zeros(C, np.int64), np.zeros(C, np.int64)
+    use = [b for b in range(B) if ids[b] >= 0]
+    for c in range(1, C):
+        class_recs = {}
+        for b in use:
+            g = gt[b, :gt_count[b]]
+            g = g[g["label"] == c]
+            class_recs[b] = dict(bbox=g["box"], difficult=g["difficult"] != 0, det=np.zeros(g.size, bool))
+            npos[c] += int((g["difficult"] == 0).sum())
+        img = np.concatenate([np.full(counts[b, c], b, np.int64) for b in use] + [np.zeros(0, np.int64)])
+        rank = np.concatenate([np.arange(counts[b, c]) for b in use] + [np.zeros(0, np.int64)])
+        conf = np.concatenate([det[b, c, :counts[b, c], 0] for b in use] + [np.zeros(0, np.float32)])
+        bbs = np.concatenate([det[b, c, :counts[b, c], 1:] for b in use] + [np.zeros((0, 4), np.float32)])
+        order = np.lexsort((rank, ids[img], -conf.astype(np.float64)))
+        tp, fp = np.zeros(order.size), np.zeros(order.size)
+        for at, d in enumerate(order):
+            R = class_recs[int(img[d])]
+            bb, BBGT = bbs[d], R["bbox"]
+            ovmax, jmax = -np.inf, -1
+            if BBGT.shape[0] > 0:
+                ixmin, iymin = np.fmax(BBGT[:, 0], bb[0]), np.fmax(BBGT[:, 1], bb[1])
+                ixmax, iymax = np.fmin(BBGT[:, 2], bb[2]), np.fmin(BBGT[:, 3], bb[3])
+                iw, ih = np.fmax(ixmax - ixmin, np.float32(0)), np.fmax(iymax - iymin, np.float32(0))
+                inters = iw * ih
+                with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+                    uni = ((BBGT[:, 2] - BBGT[:, 0]) * (BBGT[:, 3] - BBGT[:, 1]) - inters) + (bb[2] - bb[0]) * (bb[3] - bb[1])
+                    overlaps = inters / uni
+                overlaps = np.where(np.isnan(overlaps), -np.inf, overlaps)
+                ovmax, jmax = overlaps.max(), int(overlaps.argmax())
+            if ovmax > thr:
+                if not R["difficult"][jmax]:
+                    if not R["det"][jmax]:
+                        tp[at] = 1.0
+                        R["det"][jmax] = True
+                    else:
+                        fp[at] = 1.0
+            else:
+                fp[at] = 1.0
+        tps[c], fps[c] = int(tp.sum()), int(fp.sum())
+        if npos[c] == 0:
+            continue
+        ctp, cfp = np.cumsum(tp), np.cumsum(fp)
+        keep = (tp + fp) > 0                                  # ignored rows are no points of the curve
+        rec = ctp[keep] / float(npos[c])
+        prec = ctp[keep] / np.maximum(ctp[keep] + cfp[keep], np.finfo(np.float64).eps)
+        ap[c] = voc_ap(rec, prec, use_07_metric)
+    have = npos > 0
+    return dict(ap=ap, npos=npos, tp=tps, fp=fps, images=len(use), map=float(ap[have].mean()) if have.any() else float("nan"))
+
+
+def _summarise(h, store: np.ndarray, num_classes: int, use_07_metric: bool) -> dict:
+    import ctypes as C
+    from . import _lib
+    per = (_lib.DetEvalClass * num_classes)()
+    images, mean = C.c_int64(), C.c_double()
+    _lib.check(_lib.lib().tf2_det_eval_summarise(h, store.ctypes.data, store.size, int(bool(use_07_metric)), per, C.byref(images),
+                                                 C.byref(mean)))
+    return dict(ap=np.array([p.ap for p in per]), npos=np.array([p.npos for p in per], np.int64),
+                tp=np.array([p.tp for p in per], np.int64), fp=np.array([p.fp for p in per], np.int64), images=int(images.value),
+                map=float(mean.value))
+
+
+class EvalHandle:
+    """A tf2_det_eval handle (host constants only: usable without a device) and the layout of its store."""
+
+    def __init__(self, num_classes: int, top_k: int, capacity: int, max_gt: int = 64, iou_thresh: float = 0.5):
+        import ctypes as C
+        from . import _lib
+        self.num_classes, self.top_k, self.capacity, self.max_gt, self.iou_thresh = num_classes, top_k, capacity, max_gt, iou_thresh
+        d = _lib.DetEvalDesc(C.sizeof(_lib.DetEvalDesc), num_classes, top_k, max_gt, capacity, iou_thresh)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().tf2_det_eval_create(C.byref(d), C.byref(h)))
+        self._h, self._destroy = h, _lib.lib().tf2_det_eval_destroy
+        self.store_size = int(_lib.lib().tf2_det_eval_store_size(h))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            self._destroy(h)
+            self._h = None
+
+    def views(self, store: np.ndarray) -> dict:
+        """seen [cap], npos [cap, C], scores [cap, C, K], flags [cap, C, K] of a host copy of the store (uint8 [store_size])"""
+        cap, C, K = self.capacity, self.num_classes, self.top_k
+        o1, o2, o3 = cap * 4, cap * 4 * (1 + C), cap * 4 * (1 + C + C * K)
+        return dict(seen=store[:o1].view(np.int32), npos=store[o1:o2].view(np.int32).reshape(cap, C),
+                    scores=store[o2:o3].view(np.float32).reshape(cap, C, K), flags=store[o3:o3 + cap * C * K].view(np.int8).reshape(cap, C, K))
+
+    def store_from(self, matches, slots) -> np.ndarray:
+        """the host image of a store that holds MatchResult(s) `matches` at `slots` (what the device leaves; unwritten bytes zero)"""
+        store = np.zeros(self.store_size, np.uint8)
+        v = self.views(store)
+        for m, sl in zip(matches, slots):
+            for b, s in enumerate(np.asarray(sl)):
+                if s >= 0 and m.status[b] == 0:
+                    v["seen"][s] = 1
+                    v["npos"][s], v["scores"][s], v["flags"][s] = m.npos[b], m.scores[b], m.flags[b]
+        return store
+
+    def summarise(self, store: np.ndarray, use_07_metric: bool = False) -> dict:
+        """tf2_det_eval_summarise on a host copy of the store: dict(ap, npos, tp, fp [C], images, map)"""
+        store = np.ascontiguousarray(store, np.uint8)
+        return _summarise(self._h, store, self.num_classes, use_07_metric)
+
+
+class DeviceEvaluator(EvalHandle):
+    """Detection accuracy on the device (tf2_det_eval_*, include/tf2_amd.h): the store of `capacity` image slots lives on `device`.
+      update(det, counts, gt, gt_count, slots)   one step behind DeviceDetector.run / .detect on `stream` (default: the current one):
+                       det / counts as the detector returns them, gt int32 [B, max_gt, 6] (the words of pack_ground_truth's records;
+                       a numpy record array is copied to the device), gt_count and slots int32 [B]; slots[b] is the image's place in
+                       the dataset, < 0 skips it.  Returns status int32 [B] on the device (0, or EVAL_BAD_* bits: the image was
+                       left out); flags=True returns (status, flags int8 [B, C, K]) as well.  No allocation happens inside a captured
+                       graph if status= (and flags_out=) are passed.
+      reset()          a new epoch: `seen` is zeroed, nothing else needs to be.
+      result()         one copy of the store to the host, then tf2_det_eval_summarise: dict(ap, npos, tp, fp [C], images, map)."""
+
+    def __init__(self, num_classes: int, top_k: int, capacity: int, max_gt: int = 64, iou_thresh: float = 0.5, device="cuda:0"):
+        import torch
+        super().__init__(num_classes, top_k, capacity, max_gt, iou_thresh)
+        self.device = torch.device(device)
+        self.store = torch.empty(self.store_size, dtype=torch.uint8, device=self.device)
+        self.reset()
+
+    def _dev(self, a, shape):
+        import torch
+        if not hasattr(a, "data_ptr"):
+            a = np.ascontiguousarray(a)
+            a = torch.from_numpy(a.view(np.int32).reshape(shape) if a.dtype == GT_DTYPE else a.astype(np.int32).reshape(shape))
+        a = a.to(self.device)
+        assert a.dtype == torch.int32 and a.is_contiguous() and tuple(a.shape) == shape, (a.dtype, tuple(a.shape), shape)
+        return a
+
+    def reset(self, stream=None) -> None:
+        import torch
+        from . import _lib
+        stream = stream or torch.cuda.current_stream(self.device)
+        _lib.check(_lib.lib().tf2_det_eval_store_init(self._h, self.store.data_ptr(), self.store.numel(), stream.cuda_stream))
+
+    def update(self, det, counts, gt, gt_count, slots, stream=None, flags: bool = False, status=None, flags_out=None):
+        import torch
+        from . import _lib
+        B, C, K = det.shape[0], self.num_classes, self.top_k
+        assert tuple(det.shape) == (B, C, K, 5) and det.dtype == torch.float32 and det.is_contiguous() and det.device == self.device
+        assert tuple(counts.shape) == (B, C) and counts.dtype == torch.int32 and counts.is_contiguous() and counts.device == self.device
+        stream = stream or torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(stream):
+            gt, gt_count, slots = self._dev(gt, (B, self.max_gt, 6)), self._dev(gt_count, (B,)), self._dev(slots, (B,))
+            if status is None:
+                status = torch.empty(B, dtype=torch.int32, device=self.device)
+            if flags and flags_out is None:
+                flags_out = torch.empty(B, C, K, dtype=torch.int8, device=self.device)
+            _lib.check(_lib.lib().tf2_det_eval_run(self._h, det.data_ptr(), counts.data_ptr(), gt.data_ptr(), gt_count.data_ptr(),
+                                                   slots.data_ptr(), B, self.store.data_ptr(), self.store.numel(), status.data_ptr(),
+                                                   flags_out.data_ptr() if flags_out is not None else None, stream.cuda_stream))
+        return (status, flags_out) if flags else status
+
+    def store_host(self) -> np.ndarray:
+        return self.store.cpu().numpy()
+
+    def result(self, use_07_metric: bool = False) -> dict:
+        return self.summarise(self.store_host(), use_07_metric)
