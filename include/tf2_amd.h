@@ -356,6 +356,46 @@ void       tf2_cls_destroy(tf2_cls* c);
 tf2_status tf2_cls_run(tf2_cls* c, const int8_t* logits_dev, int batch, int32_t* labels_dev, float* features_dev, float* probs_dev,
                        float* all_probs_dev, const int32_t* truth_dev, int32_t* rank_dev, uint64_t* tally_dev, void* hip_stream);
 
+/* ---- Face matching on the device (1:N search of a feature library, faceverify/README.md; INTEGRATION.md "Face matching on the
+ * device") ----
+ * A matcher belongs to a network handle whose only output is a 1 x 1 map of D = 2..512 channels, the embedding network (SqueezeNet
+ * 1.1 with its 1000 -> 128 row: D = 128); it reads the handle's q table at create.  The reference ships no program text for the
+ * matching, so this statement is the canonical one (tf2_amd.embed.reference_embed / reference_match / reference_tally are the host
+ * statement; every device output is bit-identical to them).  All arithmetic is IEEE float32, every operation rounded separately
+ * (no fused multiply-add), every sum taken for c ascending from +0:
+ *   embedding  f[c] = (float)out[c] / (float)(1 << sh[c]), sh[c] = -q[c] in 0..30 of the last layer's runtime Q row (exact);
+ *              s = sum_c f[c] * f[c];  e[c] = f[c] / sqrt(s), sqrt and division correctly rounded;  s == 0: e = 0, no division.
+ *   distance   d(b, n) = sum_c (e[b][c] - g[n][c])^2 to row n of the gallery, float32 [n_rows][D] row-major in device memory that the
+ *              caller owns (a feature library read from a file goes straight in; enrolling is the embed call with a row of the
+ *              gallery as its output).  A NaN distance (from a caller's row only) counts, and is reported, as +inf.
+ *   top-k      the first top_k rows by (distance ascending, row index ascending): idx_dev int32, dist_dev float32 [batch][top_k];
+ *              slots past n_rows read idx -1, dist +inf, id -1.  ids_out_dev (optional) receives gallery_ids_dev[idx], or idx where
+ *              gallery_ids_dev is NULL; emb_out_dev (optional) the queries' embeddings float32 [batch][D].
+ *   tally      uint64 [5], ACCUMULATED (the caller zeroes it), with truth_dev int32 [batch]: truth < 0 is unlabelled, nothing
+ *              counted; else {labelled, id[0] == truth, any of the top_k ids == truth, true accepts: dist[0] < threshold and
+ *              id[0] == truth, false accepts: dist[0] < threshold and id[0] != truth}.  The comparison is a strict float32 '<'; a
+ *              truth that no gallery row carries is an impostor.  Integer adds only: exact and order-independent.
+ * A match enqueues three kernels on hip_stream (embed; stage 1: a block per slab of 64 gallery rows and 32 queries keeps the slab's
+ * best top_k per query as 64-bit keys in the scratch; stage 2: a wave per query merges them): no allocation, no synchronisation,
+ * grids that depend on batch, n_rows and the handle's constants alone (graph-capturable; a captured graph fixes n_rows).  The
+ * scratch is caller-provided device memory, 8-byte aligned, of at least the stated size for (batch, n_rows); concurrent matches
+ * need their own.  Host checks, before any device call (TF2_ERR_ARG with a message unless stated): create -- desc size, null net, q
+ * table not set (TF2_ERR_STATE), a final 1 x 1 map that is the net's only output, D outside 2..512 (TF2_ERR_UNSUPPORTED), every Q of
+ * the last row in 0..30, top_k in 1..16; run -- batch >= 1, n_rows >= 1, non-null required pointers, a threshold that is not NaN,
+ * scratch_bytes below the stated size (TF2_ERR_SIZE). */
+typedef struct tf2_emb tf2_emb;
+typedef struct tf2_emb_desc {
+  uint32_t size;                    /* sizeof(tf2_emb_desc) */
+  int32_t top_k;                    /* 1..16 */
+} tf2_emb_desc;
+tf2_status tf2_emb_create(tf2_net* net, const tf2_emb_desc* d, tf2_emb** out);
+void       tf2_emb_destroy(tf2_emb* m);
+size_t     tf2_emb_scratch_size(const tf2_emb* m, int batch, int n_rows);
+tf2_status tf2_emb_embed(tf2_emb* m, const int8_t* out_i8_dev, int batch, float* rows_dev, void* hip_stream);
+tf2_status tf2_emb_match(tf2_emb* m, const int8_t* out_i8_dev, int batch, const float* gallery_dev, const int32_t* gallery_ids_dev,
+                         int n_rows, float threshold, void* scratch_dev, size_t scratch_bytes, int32_t* idx_dev, float* dist_dev,
+                         int32_t* ids_out_dev, float* emb_out_dev, const int32_t* truth_dev, uint64_t* tally_dev, void* hip_stream);
+
 /* ---- Detection accuracy on the device (the PASCAL VOC devkit protocol behind the README's SSD mAP; INTEGRATION.md "Detection accuracy
  * on the device") ----
  * The reference ships no evaluation code (ssd.py: no weights, no dataset, no eval script), so this statement is the canonical one.

@@ -74,6 +74,11 @@ class PreprocessDesc(C.Structure):
                 ("mean", C.c_float * 3), ("scale", C.c_float * 3)]
 
 
+class EmbDesc(C.Structure):
+    """tf2_emb_desc (include/tf2_amd.h)."""
+    _fields_ = [("size", C.c_uint32), ("top_k", C.c_int32)]
+
+
 class ClsDesc(C.Structure):
     """tf2_cls_desc (include/tf2_amd.h)."""
     _fields_ = [("size", C.c_uint32), ("top_k", C.c_int32)]
@@ -186,6 +191,13 @@ def lib() -> C.CDLL:
     L.tf2_cls_destroy.argtypes = [vp]
     L.tf2_cls_destroy.restype = None
     L.tf2_cls_run.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tf2_emb_create.argtypes = [vp, C.POINTER(EmbDesc), C.POINTER(vp)]
+    L.tf2_emb_destroy.argtypes = [vp]
+    L.tf2_emb_destroy.restype = None
+    L.tf2_emb_scratch_size.argtypes = [vp, C.c_int, C.c_int]
+    L.tf2_emb_scratch_size.restype = sz
+    L.tf2_emb_embed.argtypes = [vp, vp, C.c_int, vp, vp]
+    L.tf2_emb_match.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, C.c_float, vp, sz, vp, vp, vp, vp, vp, vp, vp]
     L.tf2_det_eval_create.argtypes = [C.POINTER(DetEvalDesc), C.POINTER(vp)]
     L.tf2_det_eval_destroy.argtypes = [vp]
     L.tf2_det_eval_destroy.restype = None
@@ -207,7 +219,8 @@ EXPORTED = [
     "tf2_ssd_create", "tf2_ssd_destroy", "tf2_ssd_workspace_size", "tf2_ssd_detect_scratch_size", "tf2_ssd_run", "tf2_ssd_detect",
     "tf2_preprocess", "tf2_cls_create", "tf2_cls_destroy", "tf2_cls_run",
     "tf2_det_eval_create", "tf2_det_eval_destroy", "tf2_det_eval_store_size", "tf2_det_eval_store_init", "tf2_det_eval_run",
-    "tf2_det_eval_summarise"]
+    "tf2_det_eval_summarise",
+    "tf2_emb_create", "tf2_emb_destroy", "tf2_emb_scratch_size", "tf2_emb_embed", "tf2_emb_match"]
 
 
 def parse_opts(text: str) -> dict:

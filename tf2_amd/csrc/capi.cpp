@@ -8,6 +8,7 @@
 #include "preprocess.h"
 #include "classify.h"
 #include "ssd_eval.h"
+#include "embed_match.h"
 
 using namespace tf2;
 
@@ -15,6 +16,7 @@ struct tf2_net { Net impl; };
 struct tf2_ssd { SsdDetector impl; };
 struct tf2_cls { Classifier impl; };
 struct tf2_det_eval { DetEvaluator impl; };
+struct tf2_emb { Matcher impl; };
 
 #define CHECK_NET(n)                                              \
   if (!(n)) { set_error("null tf2_net handle"); return TF2_ERR_ARG; }
@@ -322,6 +324,42 @@ tf2_status tf2_cls_run(tf2_cls* c, const int8_t* logits_dev, int batch, int32_t*
   if (!logits_dev || !labels_dev) { set_error("tf2_cls_run: null logits_dev / labels_dev"); return TF2_ERR_ARG; }
   if (!c) { set_error("null tf2_cls handle"); return TF2_ERR_ARG; }
   return c->impl.run(logits_dev, batch, labels_dev, features_dev, probs_dev, all_probs_dev, truth_dev, rank_dev, tally_dev, stream);
+}
+
+tf2_status tf2_emb_create(tf2_net* net, const tf2_emb_desc* d, tf2_emb** out) {
+  CHECK_NET(net);
+  if (!out) { set_error("tf2_emb_create: null argument"); return TF2_ERR_ARG; }
+  tf2_emb* m = new (std::nothrow) tf2_emb();
+  if (!m) { set_error("out of memory"); return TF2_ERR_SIZE; }
+  const tf2_status st = m->impl.create(&net->impl, d);
+  if (st != TF2_OK) { delete m; return st; }
+  *out = m;
+  return TF2_OK;
+}
+
+void tf2_emb_destroy(tf2_emb* m) { delete m; }
+
+size_t tf2_emb_scratch_size(const tf2_emb* m, int batch, int n_rows) { return m ? m->impl.scratch_size(batch, n_rows) : 0; }
+
+tf2_status tf2_emb_embed(tf2_emb* m, const int8_t* out_i8_dev, int batch, float* rows_dev, void* stream) {
+  if (batch < 1) { set_error("tf2_emb_embed: batch must be >= 1"); return TF2_ERR_ARG; }
+  if (!out_i8_dev || !rows_dev) { set_error("tf2_emb_embed: null out_i8_dev / rows_dev"); return TF2_ERR_ARG; }
+  if (!m) { set_error("null tf2_emb handle"); return TF2_ERR_ARG; }
+  return m->impl.embed(out_i8_dev, batch, rows_dev, stream);
+}
+
+tf2_status tf2_emb_match(tf2_emb* m, const int8_t* out_i8_dev, int batch, const float* gallery_dev, const int32_t* gallery_ids_dev,
+                         int n_rows, float threshold, void* scratch_dev, size_t scratch_bytes, int32_t* idx_dev, float* dist_dev,
+                         int32_t* ids_out_dev, float* emb_out_dev, const int32_t* truth_dev, uint64_t* tally_dev, void* stream) {
+  if (batch < 1) { set_error("tf2_emb_match: batch must be >= 1"); return TF2_ERR_ARG; }
+  if (n_rows < 1) { set_error("tf2_emb_match: n_rows must be >= 1"); return TF2_ERR_ARG; }
+  if (!out_i8_dev || !gallery_dev) { set_error("tf2_emb_match: null out_i8_dev / gallery_dev"); return TF2_ERR_ARG; }
+  if (!scratch_dev) { set_error("tf2_emb_match: null scratch_dev"); return TF2_ERR_ARG; }
+  if (!idx_dev || !dist_dev) { set_error("tf2_emb_match: null idx_dev / dist_dev"); return TF2_ERR_ARG; }
+  if (threshold != threshold) { set_error("tf2_emb_match: threshold is NaN"); return TF2_ERR_ARG; }
+  if (!m) { set_error("null tf2_emb handle"); return TF2_ERR_ARG; }
+  return m->impl.match(out_i8_dev, batch, gallery_dev, gallery_ids_dev, n_rows, threshold, scratch_dev, scratch_bytes, idx_dev, dist_dev,
+                       ids_out_dev, emb_out_dev, truth_dev, tally_dev, stream);
 }
 
 tf2_status tf2_det_eval_create(const tf2_det_eval_desc* d, tf2_det_eval** out) {
