@@ -155,7 +155,7 @@ def test_spread_regime_dual_and_empty_phases_on_resnet50(golden_dir):
 
 @pytest.mark.parametrize("regime,top", [("shift22", 22), ("shift23", 23)])
 def test_shift_boundary_regimes(regime, top):
-    """conv_shift.hip switches from v_mad_i32_i24 to a 32-bit multiply above max_shift 22 (net.hip): the layers' largest shift is
+    """conv_shift.hip switches from v_mad_i32_i24 to a 32-bit multiply above max_shift 22 (net_plan.hip): the layers' largest shift is
     exactly 22 / 23 in mode 2."""
     t, q, model, x = _tiny(regime)
     st, _, _ = regime_stats(t, q, model, x, TINY_ROWS, mode=2)

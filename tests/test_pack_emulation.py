@@ -167,7 +167,7 @@ def test_resnet50_first_layer_stem_image(golden_dir, kind):
 
 def test_resnet50_wide_tile_alternatives(golden_dir):
     """Layers with >= 256 output channels on the 14x14 / 7x7 maps are packed twice: 64-row tiles (small batches, split-K) and
-    128-row tiles (net.hip picks them when their grid fills the chip, or earlier when batches are in flight).  The alternative
+    128-row tiles (net_plan.hip picks them when their grid fills the chip, or earlier when batches are in flight).  The alternative
     entry must compute the same layer: a 1x1 expand, a 3x3 and a 1x1 reduce."""
     t = cfg.resnet50_tables()
     q = np.loadtxt(os.path.join(golden_dir, "resnet50_Q"), dtype=np.int32)

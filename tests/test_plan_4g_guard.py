@@ -4,7 +4,7 @@ Audit of the fused kernels' global addressing: conv_bfirst, conv_bband, conv_bgr
 address from a 64-bit pixel base (size_t / long long); conv_bneck's phase 2 addresses the expand's residual and output as kernel-argument
 base + ONE 32-bit byte offset ((unsigned)pix_base * Cp + channel), and conv_pwk reads and writes through 32-bit offsets as well
 (conv_pwk_eligible refuses tensors of 2^32 bytes or more).  So every launch of those two kernels must see tensors below 2^32 bytes; a
-bottleneck pair whose tensors do not fit runs as its two separate launches (Net's fuse eligibility, net.hip)."""
+bottleneck pair whose tensors do not fit runs as its two separate launches (the planner's fuse eligibility, net_plan.hip)."""
 import numpy as np
 import pytest
 

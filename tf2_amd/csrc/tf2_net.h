@@ -48,7 +48,7 @@ struct WorkPlan {
   size_t total_bytes = 0;
 };
 
-// One prepared kernel launch of a step (net.hip launch_plan): argument block + kernel selection.
+// One prepared kernel launch of a step (net_plan.hip Net::launch_plan): argument block + kernel selection.
 struct Launch {
   enum Kind { PREP, CONV, POOL, AVG, L2N } kind = CONV;
   enum Sel { SEL_MFMA2, SEL_SK, SEL_PW, SEL_PWK, SEL_PWKPAIR, SEL_SHIFT, SEL_BNECK, SEL_STEM, SEL_PAIR, SEL_SKPAIR, SEL_BGROUP, SEL_BGROUPF, SEL_BFIRST, SEL_BBAND, SEL_C3, SEL_FC, SEL_FIRST, SEL_FIRE } sel = SEL_MFMA2;
