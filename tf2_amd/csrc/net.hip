@@ -372,6 +372,9 @@ void Net::load_options() {
   o.fc_min_slabs = (int)opt("fc_min", o.fc_min_slabs);
   o.c3_mode = (int)opt("c3", o.c3_mode);
   o.c3_min_blocks = (long)opt("c3_min", o.c3_min_blocks);
+  o.img_mode = (int)opt("img", o.img_mode);             // conv_img.hip for the stride-1 rows of small maps: 0 never, 1 (default) with batches in flight, 2 always
+  o.img_min = (int)opt("img_min", o.img_min);
+  o.img_rows = (unsigned long long)opt("img_rows", 0); o.noimg_rows = (unsigned long long)opt("noimg_rows", 0);
   o.c3_min256 = (long)opt("c3_min256", o.c3_min256);
   o.c3_w9 = (int)opt("c3_w9", o.c3_w9);
   o.c3_pool = (int)opt("c3_pool", o.c3_pool);
@@ -476,6 +479,7 @@ int Net::issue(const Launch& st, const LaunchPlan* lp, const void* images, bool 
         case Launch::SEL_SKPAIR: return launch_conv_mfma_sk_pair(st.conv, st.conv2, opts.sk8_blocks, st.shape, stream);
         case Launch::SEL_BBAND: return launch_conv_bband(st.bband, st.bg_c, st.bg_m, stream);
         case Launch::SEL_C3: return launch_conv_c3(st.c3, stream);
+        case Launch::SEL_IMG: return launch_conv_img(st.img, stream);
         case Launch::SEL_FIRE: return launch_conv_fire(st.fire, stream);
         case Launch::SEL_FC: return launch_conv_fc(st.fc, stream);
         case Launch::SEL_BGROUPF: return launch_conv_bgroup_first(st.bgroup, stream);

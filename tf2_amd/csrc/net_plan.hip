@@ -189,6 +189,25 @@ bool Net::fc_at(int l, int batch) const {
   return one_window || dual;
 }
 
+// a k x k (k = 1, 3) / stride 1 / pad (k - 1) / 2 row on a square map of a shape conv_img.hip is instantiated for: a post-ReLU input
+// tensor of its own with exactly C bytes per pixel, dense one- or two-window 64-row tiles of its own, nothing behind the convolution
+// but the requantisation (no pool, average, concat slice, residual), not the network's last row (that one stores the dense logits)
+bool Net::img_at(int l) const {
+  if (l < 0 || l >= nd.n_layers - 1) return false;
+  const tf2_layer_desc& L = layers[l];
+  if (L.ipool || L.pool_en || L.endpool || L.concat >= 0 || L.add_src >= 0 || L.src < 0) return false;
+  if ((L.k != 1 && L.k != 3) || L.stride != 1 || L.dil != 1 || L.pad_h != (L.k - 1) / 2 || L.pad_w != (L.k - 1) / 2) return false;
+  if (L.H != L.W || L.OH != L.H || L.OW != L.W) return false;
+  if (layers[L.src].concat >= 0 || out_Cp[L.src] != L.C || !out_nonneg(L.src)) return false;
+  const PackLayer* pl = pack_layer(l);
+  if (!pl || pl->kind != KIND_MFMA || pl->TM != 64 || pl->w_share || pl->signed_in) return false;
+  if (pl->Cp_in != L.C || pl->Cp_in % 64 != 0 || pl->nslab != L.k * L.k * (pl->Cp_in / 64) || (long)pl->n_entries != (long)pl->n_mtiles * pl->nslab) return false;
+  if (pl->fuse_next > 0 || pl->fused_into >= 0 || pl->merge_next > 0 || pl->merged_into >= 0 || pl->fc4) return false;
+  const bool one_window = pl->n_phases == 1 && !pl->dual, dual = pl->n_phases == 2 && pl->dual;
+  if (!one_window && !dual) return false;
+  return conv_img_shape_ok(L.H, L.C, L.k);
+}
+
 // conv_stem.hip takes layer 0 when the packed image holds its x-only weight tiles (weight_pack.cpp) and the fast
 // space-to-depth prep applies; the input tensor then carries 32 bytes per pixel in the same allocation.
 bool Net::stem_selected(int batch) const {
@@ -695,6 +714,30 @@ struct Planner {
     return pool_in;
   }
 
+  // conv_img.hip takes the row over (Net::img_at): with batches in flight (img=2: one batch at a time as well -- rows() asks the group
+  // launches first, so they keep their rows) from batch img_min on; img_rows / noimg_rows (test-only) decide a row whatever img / img_min say.
+  // The kernel forms every tensor address in 64 bits; the 2^32 guard keeps its launches inside what its tests cover.
+  void img_takeover(int l, const tf2_layer_desc& L, Launch& st) {
+    if (l < 64 && ((opts.noimg_rows >> l) & 1)) return;
+    const bool forced = l < 64 && ((opts.img_rows >> l) & 1);
+    if (!(forced || (opts.img_mode && (concurrent || opts.img_mode == 2) && batch >= opts.img_min))) return;
+    if (!n.img_at(l)) return;
+    const PackLayer* pm = n.pack_layer(l);
+    Launch sc;
+    if (!(conv_step(l, sc, false) && sc.TM == 64 && pm->TM == 64)) return;
+    const ConvArgs& c = sc.conv;
+    if ((long long)batch * L.H * L.W * std::max(c.g.Cp_in, c.g.y_cp) >= (1ll << 32) || c.g.Cp_in != L.C || c.g.has_res || c.g.avg_mult) return;
+    ImgArgs& f = sc.img;
+    f.x = c.x; f.y = c.y; f.w = c.w; f.hdr = c.hdr; f.hdr_bytes = c.hdr_bytes; f.zero = c.zero;
+    f.hdr_used = round_up((5 + pm->n_phases) * 64 * 4, 1024);
+    f.B = batch; f.HW = L.H; f.C = L.C; f.k = L.k; f.n_mtiles = pm->n_mtiles;
+    f.dual = c.dual; f.relu = c.g.relu; f.fast = c.g.fast; f.dbl = c.g.dbl_out;
+    f.y_cp = c.g.y_cp; f.y_off = c.g.y_off; f.y_nvalid = c.g.y_nvalid;
+    if (f.hdr_used > f.hdr_bytes || conv_img_lds_bytes(f.HW, f.C, f.k, (size_t)f.hdr_used) > 160 * 1024) return;
+    sc.sel = Launch::SEL_IMG; sc.avg_fused = 0;
+    st = sc;
+  }
+
   // this 3x3 + its only consumer (the 1x1 expand) in one launch (conv_bneck.hip); the expand's argument block supplies the second half
   bool bneck_fuse(int l, const tf2_layer_desc& L, const PackLayer* pl, Launch& st) {
     fused_done[pl->fuse_next] = 1;
@@ -848,6 +891,7 @@ struct Planner {
     if (!fuse_now) fc_takeover(l, st);
     if (pl->fc4 && st.sel != Launch::SEL_FC) { give_up("layer " + std::to_string(l) + " is packed as 4-bit codes (fc4) but conv_fc cannot take it"); return; }
     const bool c3_pool_fused = !fuse_now && st.sel != Launch::SEL_FC && c3_takeover(l, L, st);
+    if (!fuse_now && st.sel != Launch::SEL_FC && st.sel != Launch::SEL_C3 && !st.avg_fused) img_takeover(l, L, st);
     if (fuse_now && !bneck_fuse(l, L, pl, st)) { give_up(); return; }
     if (opts.pair_mode && !fuse_now && !pair_forms(l, st)) { give_up(); return; }
     if (l == 0 && stem && !stem_step(L, pl, st)) { give_up(); return; }

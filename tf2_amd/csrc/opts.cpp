@@ -22,6 +22,7 @@ const OptSpec kOptSpecs[] = {
   {"bfirst", 0, "the first bottleneck of the 56 x 56 stage (shortcut | reduce, 3x3, expand + residual) as one launch of independent row bands (conv_bfirst.hip): 0 never, 1 (default) with batches in flight, 2 one batch at a time as well"},
   {"bband", 0, "band launches (conv_bband.hip) of identity bottlenecks: 0 never, 1 (default) with batches in flight, 2 one batch at a time as well"},
   {"c3", 0, "3x3 / 1 / pad 1 layers of big maps on conv_c3.hip: 1 (default), 0 the ring kernel; 2 / 3 force 64- / 128-channel blocks (tests)"},
+  {"img", 0, "stride-1 rows of small square maps (ResNet-50's 7 x 7 x 512 3x3 rows) on conv_img.hip (whole images per block, the input resident in LDS): 0 never, 1 (default) with batches in flight, 2 one batch at a time as well (group launches keep their rows)"},
   {"fc", 0, "whole-window layers at batch <= 32 on conv_fc.hip (weight stream): 1 (default) / 0"},
   {"fc4", 0, "pack time: conv_fc layers keep their filters as 4-bit codes in HBM (expanded in registers): 1 (default) / 0 int8 window tiles"},
   {"share", 0, "pack time: alternative tile heights share the main entry's weight tiles: 1 (default: the wide ones), 2 all, 0 none"},
@@ -33,6 +34,7 @@ const OptSpec kOptSpecs[] = {
   {"pw", 1, "conv_pw: 1 auto, 0 never"}, {"pw_slabs", 1, "conv_pw: most K slabs"}, {"pw_minpix", 1, "conv_pw: fewest pixels"},
   {"sk_kb", 1, "split-K launches of a few blocks split K over blocks as well (batch 1-4): 1 (default) / 0"}, {"sk_kb_blocks", 1, "... largest grid that takes it (default 8)"}, {"sk_kb_max", 1, "... most blocks per output tile (default 8)"}, {"sk_kb_min", 1, "... fewest (default 8: only slab lists long enough for eight parts)"}, {"stem_pk_small", 1, "conv_stem_pool_kernel at small batches: fewer pooled rows per block (>= ~192 blocks): 1 (default) / 0"}, {"q128", 1, "the input preparation reports -128s per image to conv_stem_pool_kernel (no scan of its input tile): 1 (default) / 0"}, {"pwk", 1, "conv_pwk (1x1 rows of 128 / 256 / 512 input channels: a block's weight fragments resident in registers, pixel tiles streamed through LDS): 0 never, 1 (default) with batches in flight, 2 one batch at a time as well"}, {"pwk_minpix", 1, "conv_pwk: fewest pixels"}, {"pwk_sk", 1, "conv_pwk: split-K rows as well"}, {"pwk_rows", 1, "bit mask of rows forced onto conv_pwk where the kernel can run them at all"}, {"nopwk_rows", 1, "... kept off it"}, {"pwk_slabs", 1, "conv_pwk: most K slabs of a row (2, 4 or 8)"}, {"pwk_units", 1, "conv_pwk: fewest (tile, channel part) units of a row (default 512)"}, {"pwk_pipe", 1, "conv_pwk: 0 = no requantisation between the next column group's MFMAs"}, {"pwk_slots", 1, "conv_pwk: blocks a launch aims at (0: 256, one per CU)"},
   {"sk", 1, "split-K kernel: 0 auto, 1 forced, 2 never"}, {"sk8", 1, "largest split-K grid in the 8-wave form"}, {"sk_s3", 1, "largest split-K grid on three ring stages, one batch at a time"}, {"sk_s3_conc", 1, "... with batches in flight"},
+  {"img_min", 1, "conv_img: smallest batch (default 8)"}, {"img_rows", 1, "bit mask of rows taken by conv_img whatever img / img_min say, where the kernel can run them at all"}, {"noimg_rows", 1, "... kept off it"},
   {"fc_min", 1, "conv_fc: shortest K in slabs"}, {"c3_min", 1, "conv_c3: smallest grid"}, {"c3_min_hw", 1, "conv_c3: smallest map side (default 14)"}, {"c3_min256", 1, "conv_c3: smallest grid of 256-channel blocks"},
   {"fire", 1, "a fire module (squeeze + merged expands) as one launch: 0 never, 1 wherever it fits, 2 (default) on maps >= 28 wide"},
   {"fire_pool", 1, "fire modules with a pool behind their expands: 0 never, 1 / 2 fire launch + pool launch (maps >= 56 wide / wherever fire allows), 3 (default) the pool inside the fire launch one batch at a time, 4 always"},

@@ -210,6 +210,23 @@ bool conv_c3_pick_tile(int H, int W, int* TH, int* TW);
 bool conv_c3_pick_tile_pool(int H, int W, int* TH, int* TW);
 bool conv_c3_shape_ok(int H, int W, int C, int Np, int min_hw);
 int launch_conv_c3(const C3Args& a, void* stream);
+
+// conv_img.hip: a k x k / stride 1 / pad (k - 1) / 2 row of a small square map, whole images per block: the block's input resident in LDS,
+// weight fragments straight into registers, K split over the block's eight waves
+struct ImgArgs {
+  const int8_t* x; int8_t* y;  // input [B][HW * HW][C] with exactly C bytes per pixel; output tensor
+  const int8_t* w;             // dense weight tiles [mtile * k * k * (C / 64) + tap * (C / 64) + slab][(hi | lo)][64 rows][64]
+  const int32_t* hdr;          // per m-tile header images (stride hdr_bytes); the first hdr_used bytes hold rows | lo | dshift
+  const int8_t* zero;          // C bytes: the stored form of x = 0 per input channel (ConvArgs::zero)
+  int32_t hdr_bytes, hdr_used;
+  int32_t B, HW, C, k, n_mtiles;
+  int32_t dual, relu, fast, dbl;
+  int32_t y_cp, y_off, y_nvalid;
+};
+bool conv_img_shape_ok(int HW, int C, int k);                          // the instantiated shapes
+size_t conv_img_lds_bytes(int HW, int C, int k, size_t hdr_used);
+long conv_img_blocks(int batch, int n_mtiles);
+int launch_conv_img(const ImgArgs& a, void* stream);                   // 1: shape not instantiated / does not fit
 #ifdef TF2_CHECK_DMA
 void conv_bband_check_counts(unsigned long long out[2]);      // -DTF2_CHECK_DMA builds only (vm_track.h)
 void conv_c3_check_counts(unsigned long long out[2]);

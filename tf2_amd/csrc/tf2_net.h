@@ -51,7 +51,7 @@ struct WorkPlan {
 // One prepared kernel launch of a step (net_plan.hip Net::launch_plan): argument block + kernel selection.
 struct Launch {
   enum Kind { PREP, CONV, POOL, AVG, L2N } kind = CONV;
-  enum Sel { SEL_MFMA2, SEL_SK, SEL_PW, SEL_PWK, SEL_PWKPAIR, SEL_SHIFT, SEL_BNECK, SEL_STEM, SEL_PAIR, SEL_SKPAIR, SEL_BGROUP, SEL_BGROUPF, SEL_BFIRST, SEL_BBAND, SEL_C3, SEL_FC, SEL_FIRST, SEL_FIRE } sel = SEL_MFMA2;
+  enum Sel { SEL_MFMA2, SEL_SK, SEL_PW, SEL_PWK, SEL_PWKPAIR, SEL_SHIFT, SEL_BNECK, SEL_STEM, SEL_PAIR, SEL_SKPAIR, SEL_BGROUP, SEL_BGROUPF, SEL_BFIRST, SEL_BBAND, SEL_C3, SEL_FC, SEL_FIRST, SEL_FIRE, SEL_IMG } sel = SEL_MFMA2;
   int layer = -1;
   int TM = 0, signed_in = 0, mul24 = 0, shape = 0;
   int TM2 = 0;               // SEL_PWKPAIR: the second layer's tile height
@@ -62,6 +62,7 @@ struct Launch {
   BneckArgs bneck{};
   FcArgs fc{};               // SEL_FC: a whole-window layer at batch <= 32 as a weight stream over the whole chip (conv_fc.hip)
   C3Args c3{};               // SEL_C3: a 3x3 / 1 / pad 1 layer from an LDS-resident halo tile (conv_c3.hip)
+  ImgArgs img{};             // SEL_IMG: a 3x3 / 1 / pad 1 row of a small map, whole images per block (conv_img.hip)
   BBandArgs bband{};         // SEL_BBAND: rows layer .. layer + 2 (an identity bottleneck) in one launch, no exchange between blocks
   BGroupArgs bgroup{};       // SEL_BGROUP: rows layer .. layer + 2 (an identity bottleneck) in one launch
   int bg_hw = 0, bg_c = 0, bg_m = 0;
@@ -119,6 +120,10 @@ struct RunOpts {           // run-time switches, read from the TF2_AMD_OPTS snap
   int c3_mode = 1;           // c3: 3x3 / 1 / pad 1 layers of big maps on conv_c3.hip (halo tile in LDS) instead of the ring kernel
   int c3_min_hw = 14;        // c3_min_hw: smallest map side that takes conv_c3
   long c3_min_blocks = 96;   // c3_min: smallest grid that takes it
+  int img_mode = 1;          // img: stride-1 rows of small square maps (ResNet-50's 7 x 7 x 512 3x3 rows) on conv_img.hip (whole images per block, input resident in LDS) instead of
+                             // the split-K kernel: 0 never, 1 (default) with batches in flight, 2 one batch at a time as well (the group launches keep their rows)
+  int img_min = 8;           // img_min: smallest batch that takes it (batch-1 plans keep their K-over-blocks launches)
+  unsigned long long img_rows = 0, noimg_rows = 0;   // test-only per-row switches (bit l = table row l): rows taken whatever img / img_min say, rows kept off
   int fc_mode = 1;           // fc: whole-window layers at batch <= 32 on conv_fc.hip
   int fc_min_slabs = 64;     // fc_min: shortest K (64-byte slabs) that takes it
   long c3_min256 = 200;      // c3_min256: smallest grid of 256-channel blocks (one-window layers; else 128-channel blocks)
@@ -213,6 +218,7 @@ struct Net {
   bool fire_at(int l) const;    // rows l (squeeze), l + 1, l + 2 (merged expands) are a fire module conv_fire.hip can take
   bool c3_at(int l) const;      // layer l can run on conv_c3.hip
   bool fc_at(int l, int batch) const;   // ... on conv_fc.hip
+  bool img_at(int l) const;     // ... on conv_img.hip
   bool bgroup_at(int l) const;             // rows l, l + 1, l + 2 are an identity bottleneck conv_bgroup.hip can take (tables + packed image)
   long long stat_steps = 0, stat_group_steps = 0, stat_inflight_steps = 0, stat_small_mask_steps = 0;   // tf2_net_run_stats
   void* recent_streams[8] = {};  // streams of the last calls to run(): several distinct ones = batches in flight
