@@ -321,6 +321,70 @@ enum {                              /* status_dev bits of a malformed record */
 tf2_status tf2_preprocess(const tf2_net* net, const tf2_preprocess_desc* d, const uint8_t* pixels_dev, size_t pixels_bytes,
                           const tf2_image_src* srcs_dev, int batch, int out_q, void* out_dev, int32_t* status_dev, void* stream);
 
+/* ---- Second-stage crops on the device (the detect -> crop -> embed -> match cascade of faceverify/README.md; INTEGRATION.md
+ * "Second-stage crops on the device") ----
+ * The step between a detector's det / counts (tf2_ssd_run) and a second network's input: tf2_roi_select picks boxes into a table
+ * of tf2_roi records in device memory, tf2_roi_crop resamples each record's box out of the SOURCE pixels (the uint8 buffer and
+ * tf2_image_src records tf2_preprocess read; their resize_* and crop_* fields are not used) into one image of net2's input.  The
+ * reference ships no program text for this step, so this statement is the canonical one (tf2_amd.roi.reference_select /
+ * reference_crop are the host statement; every device output is bit-identical to them).
+ * Select, per source image b: the candidates are the rows (c, r) of det[b] with bit c of class_mask set, r < min(counts[b][c],
+ * top_k), score > min_score (strict float32; a NaN never passes) and a valid transformed box; the best max_rois of them by (score
+ * descending, class ascending, rank ascending) -- a total order on the float32 values -- go to slots b * max_rois + 0 .. n-1, n to
+ * roi_counts_dev[b], and the image's other slots get the empty record (image = -1, every other field 0).  Every slot is written by
+ * every call with ordinary stores: no atomics, no dependence on replay order.  The transform, in double from the float32 det
+ * values (x1, y1, x2, y2) and the source size (w, h) of srcs_dev[b], every operation rounded separately:
+ *   X1 = x1 * w, X2 = x2 * w, Y1 = y1 * h, Y2 = y2 * h;  cx = (X1 + X2) / 2, cy = (Y1 + Y2) / 2;
+ *   bw = (X2 - X1) * expand_w, bh = (Y2 - Y1) * expand_h;  square: bw = bh = (bh > bw ? bh : bw);
+ *   x0 = cx - bw / 2, x1' = cx + bw / 2, y0 = cy - bh / 2, y1' = cy + bh / 2;
+ *   clip: v = v < 0 ? 0 : (v > limit ? limit : v) with limit w for x and h for y (a NaN stays a NaN);  then one rounding to float32.
+ * The box is valid iff the four float32 values are finite and x1' - x0 >= 1 and y1' - y0 >= 1, evaluated in double on the float32
+ * values.  A source record whose h or w is outside 1..32767 gives its image zero ROIs (nothing else of the record is read).
+ * Crop, per slot s with record R, source r = srcs_dev[R.image] and output pixel (y, x) of net2's image_h x image_w (OH x OW) input,
+ * in double, every operation rounded separately:
+ *   sy = ((double)R.y1 - (double)R.y0) / OH;  t = (y + 0.5) * sy;  t = (double)R.y0 + t;  fy = t - 0.5;  the same for columns;
+ * then tf2_preprocess's rule from fy on: y0 = floor(fy), wy = (float)(fy - y0), the clamps at 0 and r.h - 1 with weight 0 (a box may
+ * leave the image: it reads the edge pixels), the float32 interpolation, round_resized, (r - mean[c]) * scale[c], and for out_q = 1
+ * the int8 quantisation with net2's 2^-Q0.  R = (0, 0, w, h) is tf2_preprocess with resize = (OH, OW) and crop (0, 0), bit for bit.
+ * out_dev is float32 or int8 [n_slots][3][OH][OW].
+ * Device checks: the table and the source records are device data, so each block validates its slot before it reads a pixel and
+ * status_dev[s] receives 0 or TF2_ROI_* bits: EMPTY alone for image == -1; otherwise BAD_IMAGE (image outside 0..batch-1; no source
+ * record is read), BAD_BOX (the validity rule above) and, for an image inside the batch, BAD_SRC (srcs_dev[image] fails the size /
+ * pitch / offset / extent rule of tf2_preprocess) in any combination.  A slot with a nonzero status is all zeros and none of its
+ * pixels is read; no read leaves [pixels_dev, pixels_dev + pixels_bytes).
+ * Host checks (TF2_ERR_ARG with a message, before any device call): select -- desc size, num_classes 2..256, top_k 1..256, max_rois
+ * 1..64, a class_mask that is empty, has bit 0 (background) set or a bit at or above num_classes, min_score finite and >= 0, expand
+ * factors finite and > 0, square and clip 0 or 1, batch >= 1, non-null pointers; crop -- every check of tf2_preprocess (on net2),
+ * n_slots >= 1, non-null rois_dev.  Select enqueues one kernel of `batch` blocks, crop one of n_slots * ceil(OH * OW / 1024) blocks
+ * of 256 threads: grids that depend on batch, max_rois and net2's image size alone, no allocation, no synchronisation, no scratch
+ * (graph-capturable: a captured detect + select + crop + embed + match replays on refilled pixels and records). */
+typedef struct tf2_roi {            /* one slot of the ROI table, 32 bytes, in DEVICE memory */
+  int32_t image;                    /* index into srcs_dev; -1: empty slot */
+  int32_t cls, rank;                /* the det row the box came from */
+  float score;
+  float x0, y0, x1, y1;             /* the box in source pixels (pixel i covers [i, i + 1)) */
+} tf2_roi;
+typedef struct tf2_roi_desc {
+  uint32_t size;                    /* sizeof(tf2_roi_desc) */
+  int32_t num_classes, top_k;       /* layout of det / counts: 2..256, 1..256 */
+  uint32_t class_mask[8];           /* bit c: class c is taken; bit 0 (background) clear, at least one bit set below num_classes */
+  float min_score;                  /* finite, >= 0 */
+  int32_t max_rois;                 /* 1..64 per source image */
+  float expand_w, expand_h;         /* finite, > 0; 1 = the box itself */
+  int32_t square, clip;             /* 0 / 1 */
+} tf2_roi_desc;
+enum {                              /* status_dev bits of a slot that was not cropped */
+  TF2_ROI_EMPTY = 1,                /* image == -1 */
+  TF2_ROI_BAD_IMAGE = 2,            /* image outside 0..batch-1 and not -1 */
+  TF2_ROI_BAD_BOX = 4,              /* a coordinate not finite, or a side below 1 */
+  TF2_ROI_BAD_SRC = 8               /* srcs_dev[image] fails the size / pitch / offset / extent rule */
+};
+tf2_status tf2_roi_select(const tf2_roi_desc* d, const float* det_dev, const int32_t* counts_dev, const tf2_image_src* srcs_dev,
+                          int batch, tf2_roi* rois_dev, int32_t* roi_counts_dev, void* hip_stream);
+tf2_status tf2_roi_crop(const tf2_net* net2, const tf2_preprocess_desc* d, const uint8_t* pixels_dev, size_t pixels_bytes,
+                        const tf2_image_src* srcs_dev, int batch, const tf2_roi* rois_dev, int n_slots, int out_q, void* out_dev,
+                        int32_t* status_dev, void* hip_stream);
+
 /* ---- Classification on the device (Evaluation, network_helper.cpp:143-207; INTEGRATION.md "Classification on the device") ----
  * A classifier belongs to a network handle whose final map is 1 x 1 (it reads the handle's q table at create: a later set_q needs
  * a new classifier).  Per image, from the int8 logits [batch][n] a run writes (n = N of the last row) and the runtime Q row of the

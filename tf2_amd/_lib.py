@@ -74,6 +74,19 @@ class PreprocessDesc(C.Structure):
                 ("mean", C.c_float * 3), ("scale", C.c_float * 3)]
 
 
+class Roi(C.Structure):
+    """tf2_roi (include/tf2_amd.h): one slot of the ROI table, in device memory."""
+    _fields_ = [("image", C.c_int32), ("cls", C.c_int32), ("rank", C.c_int32), ("score", C.c_float), ("x0", C.c_float),
+                ("y0", C.c_float), ("x1", C.c_float), ("y1", C.c_float)]
+
+
+class RoiDesc(C.Structure):
+    """tf2_roi_desc (include/tf2_amd.h)."""
+    _fields_ = [("size", C.c_uint32), ("num_classes", C.c_int32), ("top_k", C.c_int32), ("class_mask", C.c_uint32 * 8),
+                ("min_score", C.c_float), ("max_rois", C.c_int32), ("expand_w", C.c_float), ("expand_h", C.c_float),
+                ("square", C.c_int32), ("clip", C.c_int32)]
+
+
 class EmbDesc(C.Structure):
     """tf2_emb_desc (include/tf2_amd.h)."""
     _fields_ = [("size", C.c_uint32), ("top_k", C.c_int32)]
@@ -187,6 +200,8 @@ def lib() -> C.CDLL:
     L.tf2_ssd_run.argtypes = [vp, vp, C.c_int, C.c_int, vp, sz, vp, vp, vp, vp, vp, vp, vp]
     L.tf2_ssd_detect.argtypes = [vp, vp, vp, C.c_int, vp, sz, vp, vp, vp]
     L.tf2_preprocess.argtypes = [vp, C.POINTER(PreprocessDesc), vp, sz, vp, C.c_int, C.c_int, vp, vp, vp]
+    L.tf2_roi_select.argtypes = [C.POINTER(RoiDesc), vp, vp, vp, C.c_int, vp, vp, vp]
+    L.tf2_roi_crop.argtypes = [vp, C.POINTER(PreprocessDesc), vp, sz, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp]
     L.tf2_cls_create.argtypes = [vp, C.POINTER(ClsDesc), C.POINTER(vp)]
     L.tf2_cls_destroy.argtypes = [vp]
     L.tf2_cls_destroy.restype = None
@@ -217,7 +232,7 @@ EXPORTED = [
     "tf2_net_packed_adopt", "tf2_net_bind_device", "tf2_net_workspace_size", "tf2_net_logits_size", "tf2_net_reload_options", "tf2_net_run",
     "tf2_net_run_q", "tf2_net_run_ex", "tf2_net_run_stats", "tf2_net_poll_error", "tf2_net_describe_launches", "tf2_net_describe_workspace", "tf2_net_read_layer", "tf2_net_profile", "tf2_net_profile_read", "tf2_net_profile_loop_read", "tf2_topk",
     "tf2_ssd_create", "tf2_ssd_destroy", "tf2_ssd_workspace_size", "tf2_ssd_detect_scratch_size", "tf2_ssd_run", "tf2_ssd_detect",
-    "tf2_preprocess", "tf2_cls_create", "tf2_cls_destroy", "tf2_cls_run",
+    "tf2_preprocess", "tf2_roi_select", "tf2_roi_crop", "tf2_cls_create", "tf2_cls_destroy", "tf2_cls_run",
     "tf2_det_eval_create", "tf2_det_eval_destroy", "tf2_det_eval_store_size", "tf2_det_eval_store_init", "tf2_det_eval_run",
     "tf2_det_eval_summarise",
     "tf2_emb_create", "tf2_emb_destroy", "tf2_emb_scratch_size", "tf2_emb_embed", "tf2_emb_match"]

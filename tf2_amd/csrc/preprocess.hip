@@ -14,17 +14,12 @@
 #include <string>
 #include "tf2_device.h"
 #include "tf2_net.h"
-#include "input_quant.h"
+#include "resample.h"
 #include "preprocess.h"
 
 namespace tf2 {
 
 namespace {
-
-constexpr int kPrepThreads = 256;
-constexpr int kPrepPix = 4;                      // output pixels per thread
-constexpr int kPrepBlockPix = kPrepThreads * kPrepPix;
-constexpr int kMaxSide = 32767;
 
 struct PreprocessArgs {
   const uint8_t* pixels;
@@ -37,53 +32,12 @@ struct PreprocessArgs {
   float mean0, mean1, mean2, scale0, scale1, scale2, trans;
 };
 
-// TF2_PREP_* bits of one record (0: valid).  The extent is tested only when size, pitch and offset are sane, in 64 bits and without
-// overflow: offset <= pixels_bytes and (h - 1) * pitch + w * pb <= pixels_bytes - offset.
-__device__ __forceinline__ int record_status(const tf2_image_src& r, const PreprocessArgs& a) {
-  int st = 0;
-  if (r.h < 1 || r.h > kMaxSide || r.w < 1 || r.w > kMaxSide) st |= TF2_PREP_BAD_SIZE;
-  if ((long long)r.row_pitch < (long long)r.w * a.pb) st |= TF2_PREP_BAD_PITCH;
-  if (r.offset < 0) st |= TF2_PREP_BAD_OFFSET;
-  if (st == 0) {
-    const unsigned long long span = (unsigned long long)((long long)(r.h - 1) * r.row_pitch + (long long)r.w * a.pb);
-    const unsigned long long off = (unsigned long long)r.offset;
-    if (off > a.pixels_bytes || span > a.pixels_bytes - off) st |= TF2_PREP_OUT_OF_BUFFER;
-  }
-  if (r.resize_h < 1 || r.resize_h > kMaxSide || r.resize_w < 1 || r.resize_w > kMaxSide) st |= TF2_PREP_BAD_RESIZE;
-  if (r.crop_y < 0 || r.crop_x < 0 || (long long)r.crop_y + a.OH > r.resize_h || (long long)r.crop_x + a.OW > r.resize_w)
-    st |= TF2_PREP_BAD_CROP;
-  return st;
-}
-
-// source tap pair and weight of output coordinate i (crop already added): double geometry, float32 weight, edge clamp
-__device__ __forceinline__ void src_coord(int i, double ratio, int n, int& i0, int& i1, float& w) {
-  const double f = ((double)i + 0.5) * ratio - 0.5;
-  const double fl = floor(f);
-  w = (float)(f - fl);
-  int k = (int)fl;
-  if (fl < 0.0) { k = 0; w = 0.0f; }
-  else if (k >= n - 1) { k = n - 1; w = 0.0f; }
-  i0 = k;
-  i1 = k + 1 < n ? k + 1 : n - 1;
-}
-
-__device__ __forceinline__ float lerp_px(float p00, float p01, float p10, float p11, float wx, float wy, int round_resized) {
-  const float top = p00 * (1.0f - wx) + p01 * wx;
-  const float bot = p10 * (1.0f - wx) + p11 * wx;
-  float r = top * (1.0f - wy) + bot * wy;
-  if (round_resized) {
-    r = rintf(r);
-    r = r < 0.0f ? 0.0f : (r > 255.0f ? 255.0f : r);
-  }
-  return r;
-}
-
 template <bool OUT_Q, bool VEC>
 __global__ __launch_bounds__(kPrepThreads) void preprocess_kernel(PreprocessArgs a) {
   const int b = blockIdx.x / a.blocks_per_image;
   const int p0 = (blockIdx.x - b * a.blocks_per_image) * kPrepBlockPix + threadIdx.x * kPrepPix;
   const tf2_image_src r = a.srcs[b];
-  const int st = record_status(r, a);
+  const int st = record_status(r, a.pb, a.pixels_bytes, a.OH, a.OW);
   if (blockIdx.x == b * a.blocks_per_image && threadIdx.x == 0) a.status[b] = st;
 
   float v[3][kPrepPix];
@@ -103,66 +57,38 @@ __global__ __launch_bounds__(kPrepThreads) void preprocess_kernel(PreprocessArgs
       float wy, wx;
       src_coord(y + r.crop_y, ry, r.h, y0, y1, wy);
       src_coord(x + r.crop_x, rx, r.w, x0, x1, wx);
-      const uint8_t* const row0 = base + (long long)y0 * r.row_pitch;
-      const uint8_t* const row1 = base + (long long)y1 * r.row_pitch;
-      const int c0 = x0 * a.pb, c1 = x1 * a.pb;
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-        const float q = lerp_px((float)row0[c0 + ch[c]], (float)row0[c1 + ch[c]], (float)row1[c0 + ch[c]], (float)row1[c1 + ch[c]],
-                                wx, wy, a.round_resized);
-        v[c][j] = (q - mean[c]) * scale[c];
-      }
+      gather_px(base, r.row_pitch, a.pb, ch, y0, y1, wy, x0, x1, wx, a.round_resized, mean, scale, v, j);
     }
   }
 
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    const long long at = ((long long)b * 3 + c) * a.plane + p0;
-    if (OUT_Q) {
-      int8_t* const y = reinterpret_cast<int8_t*>(a.out) + at;
-      int q[kPrepPix];
-#pragma unroll
-      for (int j = 0; j < kPrepPix; j++) q[j] = st != 0 ? 0 : quant_input(v[c][j], a.trans);
-      if (VEC) {
-        if (p0 < a.plane)
-          *reinterpret_cast<uint32_t*>(y) = (uint32_t)(q[0] & 0xff) | (uint32_t)(q[1] & 0xff) << 8 | (uint32_t)(q[2] & 0xff) << 16 |
-                                            (uint32_t)(q[3] & 0xff) << 24;
-      } else {
-#pragma unroll
-        for (int j = 0; j < kPrepPix; j++)
-          if (p0 + j < a.plane) y[j] = (int8_t)q[j];
-      }
-    } else {
-      float* const y = reinterpret_cast<float*>(a.out) + at;
-      if (VEC) {
-        if (p0 < a.plane) *reinterpret_cast<float4*>(y) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < kPrepPix; j++)
-          if (p0 + j < a.plane) y[j] = v[c][j];
-      }
-    }
-  }
+  store_px<OUT_Q, VEC>(a.out, b, a.plane, p0, v, a.trans, st);
 }
 
 }  // namespace
 
+// the refusals tf2_preprocess and tf2_roi_crop share, in the order they are tested: the message, or "" when the call may go on
+std::string preprocess_refusal(const Net& net, const tf2_preprocess_desc* d, int batch, int out_q, bool pointers_ok) {
+  if (!d) return "null desc";
+  if (d->size != sizeof(tf2_preprocess_desc)) return "desc size " + std::to_string(d->size) + ", expected sizeof(tf2_preprocess_desc)";
+  if (d->pixel_bytes != 3 && d->pixel_bytes != 4) return "pixel_bytes must be 3 or 4";
+  for (int c = 0; c < 3; c++)
+    if (d->src_channel[c] < 0 || d->src_channel[c] >= d->pixel_bytes) return "src_channel[" + std::to_string(c) + "] outside 0..pixel_bytes-1";
+  for (int c = 0; c < 3; c++)
+    if (!std::isfinite(d->mean[c]) || !std::isfinite(d->scale[c])) return "means and scales must be finite";
+  if (d->round_resized != 0 && d->round_resized != 1) return "round_resized must be 0 or 1";
+  if (net.nd.image_c != 3) return "the net's image_c is " + std::to_string(net.nd.image_c) + ", not 3";
+  if (batch < 1) return "batch must be >= 1";
+  if (out_q != 0 && out_q != 1) return "out_q must be 0 or 1";
+  if (!pointers_ok) return "null device pointer";
+  if (out_q && net.q.empty()) return "out_q = 1 needs the q table (tf2_net_set_q)";
+  return "";
+}
+
 tf2_status preprocess(const Net& net, const tf2_preprocess_desc* d, const uint8_t* pixels, size_t pixels_bytes, const tf2_image_src* srcs,
                       int batch, int out_q, void* out, int32_t* status, void* stream) {
   auto refuse = [](const std::string& m) { set_error("tf2_preprocess: " + m); return TF2_ERR_ARG; };
-  if (!d) return refuse("null desc");
-  if (d->size != sizeof(tf2_preprocess_desc)) return refuse("desc size " + std::to_string(d->size) + ", expected sizeof(tf2_preprocess_desc)");
-  if (d->pixel_bytes != 3 && d->pixel_bytes != 4) return refuse("pixel_bytes must be 3 or 4");
-  for (int c = 0; c < 3; c++)
-    if (d->src_channel[c] < 0 || d->src_channel[c] >= d->pixel_bytes) return refuse("src_channel[" + std::to_string(c) + "] outside 0..pixel_bytes-1");
-  for (int c = 0; c < 3; c++)
-    if (!std::isfinite(d->mean[c]) || !std::isfinite(d->scale[c])) return refuse("means and scales must be finite");
-  if (d->round_resized != 0 && d->round_resized != 1) return refuse("round_resized must be 0 or 1");
-  if (net.nd.image_c != 3) return refuse("the net's image_c is " + std::to_string(net.nd.image_c) + ", not 3");
-  if (batch < 1) return refuse("batch must be >= 1");
-  if (out_q != 0 && out_q != 1) return refuse("out_q must be 0 or 1");
-  if (!pixels || !srcs || !out || !status) return refuse("null device pointer");
-  if (out_q && net.q.empty()) return refuse("out_q = 1 needs the q table (tf2_net_set_q)");
+  const std::string why = preprocess_refusal(net, d, batch, out_q, pixels && srcs && out && status);
+  if (!why.empty()) return refuse(why);
 
   PreprocessArgs a{};
   a.pixels = pixels; a.pixels_bytes = pixels_bytes; a.srcs = srcs; a.out = out; a.status = status;

@@ -144,23 +144,28 @@ def record_status(srcs, pixel_bytes: int, pixels_bytes: int, out_hw) -> np.ndarr
     return out
 
 
-def _taps(n_out: int, start: int, n_src: int, n_resized: int):
-    f = (np.arange(n_out, dtype=np.int64) + start + 0.5) * (n_src / n_resized) - 0.5
-    i0 = np.floor(f)
-    w = (f - i0).astype(np.float32)
-    lo, hi = i0 < 0, i0 >= n_src - 1
-    i0 = i0.astype(np.int64)
-    i0[lo], w[lo] = 0, 0
-    i0[hi], w[hi] = n_src - 1, 0
+def taps_of(f, n_src: int):
+    """(i0, i1, w) of float64 source coordinates f on an axis of n_src samples: i0 = floor(f), float32 weight, both edge clamps with
+    weight 0 (decided on the float64 value: a coordinate far outside the image is as good as any)"""
+    f = np.asarray(f, np.float64)
+    fl = np.floor(f)
+    w = (f - fl).astype(np.float32)
+    lo, hi = fl < 0, fl >= n_src - 1
+    i0 = np.clip(fl, 0, n_src - 1).astype(np.int64)
+    w[lo | hi] = 0
     return i0, np.minimum(i0 + 1, n_src - 1), w
 
 
-def resize_one(img, rh: int, rw: int, cy: int, cx: int, oh: int, ow: int, round_resized: bool = False) -> np.ndarray:
-    """The statement's resize + crop of one HWC uint8 image (all its channels): float32 [C, oh, ow] (0..255 units)"""
+def _taps(n_out: int, start: int, n_src: int, n_resized: int):
+    return taps_of((np.arange(n_out, dtype=np.int64) + start + 0.5) * (n_src / n_resized) - 0.5, n_src)
+
+
+def lerp_taps(img, ytaps, xtaps, round_resized: bool = False) -> np.ndarray:
+    """The statement's interpolation of one HWC uint8 image (all its channels) at row taps (y0, y1, wy) and column taps (x0, x1, wx):
+    float32 [C, len(y0), len(x0)] (0..255 units), optionally rounded to bytes"""
     img = np.asarray(img)
     h, w = img.shape[:2]
-    y0, y1, wy = _taps(oh, cy, h, rh)
-    x0, x1, wx = _taps(ow, cx, w, rw)
+    (y0, y1, wy), (x0, x1, wx) = ytaps, xtaps
     p = np.moveaxis(img.reshape(h, w, -1), 2, 0).astype(np.float32)
     one = np.float32(1)
     wx, wy = wx[None, None, :], wy[None, :, None]
@@ -170,6 +175,19 @@ def resize_one(img, rh: int, rw: int, cy: int, cx: int, oh: int, ow: int, round_
     if round_resized:
         r = np.clip(np.rint(r), 0, 255).astype(np.float32)
     return r
+
+
+def resize_one(img, rh: int, rw: int, cy: int, cx: int, oh: int, ow: int, round_resized: bool = False) -> np.ndarray:
+    """The statement's resize + crop of one HWC uint8 image (all its channels): float32 [C, oh, ow] (0..255 units)"""
+    h, w = np.asarray(img).shape[:2]
+    return lerp_taps(img, _taps(oh, cy, h, rh), _taps(ow, cx, w, rw), round_resized)
+
+
+def source_image(pixels, r, pixel_bytes: int, src_channel) -> np.ndarray:
+    """the net's channels of the image a (valid) record describes: uint8 [h, w, 3]"""
+    h, w, pitch, off = int(r["h"]), int(r["w"]), int(r["row_pitch"]), int(r["offset"])
+    rows = np.stack([pixels[off + y * pitch: off + y * pitch + w * pixel_bytes] for y in range(h)]).reshape(h, w, pixel_bytes)
+    return rows[:, :, list(src_channel)]
 
 
 def reference(pixels, srcs, out_hw, pixel_bytes: int, src_channel, mean, scale, round_resized: bool = False, q0: Optional[int] = None):
@@ -184,10 +202,8 @@ def reference(pixels, srcs, out_hw, pixel_bytes: int, src_channel, mean, scale, 
     for b, r in enumerate(srcs):
         if status[b]:
             continue
-        h, w, pitch, off = int(r["h"]), int(r["w"]), int(r["row_pitch"]), int(r["offset"])
-        rows = np.stack([pixels[off + y * pitch: off + y * pitch + w * pixel_bytes] for y in range(h)]).reshape(h, w, pixel_bytes)
-        img = rows[:, :, list(src_channel)]
-        res = resize_one(img, int(r["resize_h"]), int(r["resize_w"]), int(r["crop_y"]), int(r["crop_x"]), oh, ow, round_resized)
+        res = resize_one(source_image(pixels, r, pixel_bytes, src_channel), int(r["resize_h"]), int(r["resize_w"]), int(r["crop_y"]),
+                         int(r["crop_x"]), oh, ow, round_resized)
         out[b] = (res - m32[:, None, None]) * s32[:, None, None]
     if q0 is not None:
         q = quant_input(out, trans_of(q0))
