@@ -642,6 +642,20 @@ def test_group_launches_with_other_packed_forms(r50, monkeypatch, pack_switch):
     np.testing.assert_array_equal(rig.run(x32, keep_all=False)[:2], rig.ref.logits(rig.ref.run(x32[:2])))
 
 
+def test_group_launches_of_one_window_rows(r50, monkeypatch):
+    """The group kernels' one-window instantiations: with a Q file without per-channel spread no row of the identity bottlenecks is a
+    two-window layer, so the 28 x 28 and 7 x 7 group launches (one bottleneck each: the 7 x 7 one with and without the global average)
+    are the instantiations the shipped Q file never selects.  Every layer against the oracle at batch 2."""
+    set_opts(monkeypatch, bgroup="1", bgroup_chain="1", bgroup_min7="1", bgroup_min14="1", bgroup_min28="1", bgroup_min56f="1", bfirst="1", alt_conc="0")
+    t = r50[0]
+    q = synth.synth_q_values(t, 5, spread=0)
+    rig = Rig(t, q, synth.synth_model(t, q, 0), 0)
+    k = {r["layer"]: r["kernel"] for r in rig.net.describe_launches(2, 0) if "conv_bgroup" in r["kernel"]}
+    assert set(k) == {1, 15, 18, 21, 28, 31, 34, 37, 40, 47, 50} and not any("dual" in v for v in k.values()), k
+    assert "conv_bgroup28_kernel" in k[15] and "conv_bgroup7_kernel" in k[47] and "global average" not in k[47] and "global average" in k[50]
+    rig.check_all_layers(synth.synth_images(t, 2, 83))
+
+
 
 
 @pytest.mark.parametrize("form", ["in_flight", "alone", "single_window", "generic"])

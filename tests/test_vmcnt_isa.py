@@ -64,12 +64,18 @@ def test_the_checker_sees_a_wait_that_is_one_load_too_generous(isa_files):
 
 
 def test_no_vmcnt_literal_left_in_the_dma_kernels():
-    """every hand-written vmcnt wait of the DMA kernels goes through vm_track.h (vmcnt(0) drains excepted)"""
-    for f in ("conv_bband.hip", "conv_c3.hip"):
-        src = open(os.path.join(ROOT, "tf2_amd", "csrc", f)).read()
+    """every hand-written vmcnt wait of every conv kernel goes through vm_track.h's vm_wait<N> (vmcnt(0) drains excepted): no literal
+    count, no private chain of prepared literals"""
+    csrc = os.path.join(ROOT, "tf2_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if f.startswith("conv_") and f.endswith(".hip"))
+    assert len(files) >= 14 and {"conv_bband.hip", "conv_c3.hip", "conv_mfma2.hip", "conv_mfma_sk.hip", "conv_bgroup.hip"} <= set(files)
+    for f in files:
+        src = open(os.path.join(csrc, f)).read()
         lits = [m.group(1) for m in re.finditer(r"s_waitcnt[^\"]*vmcnt\((\d+)\)", src)]
         assert all(v == "0" for v in lits), (f, lits)
-        assert "vm_wait<" in src
+        assert not re.search(r"\bvoid\s+\w*wait_vmcnt\s*\(", src), f
+    for f in ("conv_bband.hip", "conv_c3.hip"):
+        assert "vm_wait<" in open(os.path.join(csrc, f)).read()
 
 
 def test_the_two_block_per_cu_bottleneck_kernels_compile_without_scratch(isa_files):

@@ -27,15 +27,9 @@
 #include "tf2_internal.h"
 #include "tf2_device.h"
 #include "requant_epilogue.h"
-#include "vm_track.h"
+#include "lds_tile.h"
 
 namespace tf2 {
-
-using i32x4 = int __attribute__((ext_vector_type(4)));
-using i32x16 = int __attribute__((ext_vector_type(16)));
-
-#define TF2_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define TF2_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
 #ifdef TF2_CHECK_DMA
 TF2_DMA_CHECK_COUNTERS(g_bband_dma_check);
@@ -62,20 +56,10 @@ struct BbSched {
   static constexpr int wait_n(int c) { return vm_min(since_dma(c), (SC - 1 < 2 ? SC - 1 : 2) * frag_loads(c * SC - 1)); }
 };
 
-template <int T, int N, class F>
-__device__ __forceinline__ void bb_static_for(F& fn) {
-  if constexpr (T < N) { fn(std::integral_constant<int, T>{}); bb_static_for<T + 1, N>(fn); }
-}
-
 constexpr int kBbPF = 2;                     // weight fragments in flight ahead of their MFMAs (steps)
 
-// LDS-DMA as inline assembly: the compiler's wait-count pass does not know these loads, so it neither drains the queue (vmcnt(0))
-// in front of the next LDS read nor orders them against anything -- every wait for them is written out below (the counter is in
-// order: a counted wait for a younger ordinary load covers every older DMA)
-__device__ __forceinline__ void bb_dma16(const int8_t* src, int8_t* lds_dst) {
-  const unsigned l = (unsigned)(unsigned long long)TF2_LDS_PTR(lds_dst);
-  asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(src), "s"(l) : "memory", "m0");
-}
+// The LDS-DMAs are issued with dma16_hidden (vm_track.h): the compiler's wait-count pass does not know them, and every wait for them is
+// written out below.
 
 // M: channels of the intermediates; WN: pixel-tile columns of the wave grid; NT0 / NT1: 32-pixel column tiles of the halo band
 // ((R + 2) * W <= 32 NT0) and of the band itself (R * W <= 32 NT1); SC: channel slabs per chunk of the input stream
@@ -136,12 +120,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void conv_bband_kernel(BBandArgs a
   int8_t* const hdr3 = hdr2 + (M >> tms2) * hst2;
 
   // XCD-aware remap: the bands of one image on one XCD (they share halo rows of the input and, all of them, the weights)
-  int bid = blockIdx.x;
-  {
-    const int nblk = gridDim.x;
-    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, within = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
-  }
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int img = bid / a.tiles_per_img;
   const int r0 = (bid - img * a.tiles_per_img) * R;
   const int rows = (H - r0) < R ? (H - r0) : R;          // valid output rows of this band
@@ -151,17 +130,16 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void conv_bband_kernel(BBandArgs a
   const long long pix0 = pix_base - W;                   // ... of halo-band pixel 0 (may lie outside the image: never dereferenced then)
 
   long long* const dbg = a.dbg ? a.dbg + (size_t)blockIdx.x * 16 : nullptr;       // tools/bband_timeline.py: 100 MHz wall clock per phase
-#define BB_STAMP(i) do { if (dbg && tid == 0) dbg[i] = (long long)wall_clock64(); } while (0)
-  BB_STAMP(0);
+  TF2_BLOCK_STAMP(dbg, 0);
 
-  // LDS-DMA: lane l fills pixel row l >> 2, slot l & 3 of a 16-pixel group, which holds chunk slot ^ ((row >> 2) & 3)
-  const int chunk = (lane & 3) ^ ((lane >> 4) & 3), drow = lane >> 2;
+  // LDS-DMA: what this lane fetches of a 16-pixel group of a swizzled [pixel][64] slab (lds_tile.h)
+  const int chunk = dma_lane_chunk(lane), drow = dma_lane_row(lane);
 
   // ---- prologue -----------------------------------------------------------------------------------------------------------
   // (1) the halo tile filled with the stored form of x = 0 (the 3x3's pad row): borders and rows outside the image stay that way
   for (int gi = wave; gi < n_grp_h * KS2; gi += NW) {
     const int s = gi / n_grp_h, grp = gi - s * n_grp_h;
-    bb_dma16(a.zero2 + s * 64 + (grp / (n_grp_h / 4)) * 16, mid1 + s * slabb + grp * 1024);
+    dma16_hidden(a.zero2 + s * 64 + (grp / (n_grp_h / 4)) * 16, mid1 + s * slabb + grp * 1024);
   }
   // (2) the input stream: chunk c = channel slabs [c * SC, (c + 1) * SC) of the NP0 halo-band pixels -> [slab][pixel][64] swizzled
   auto issue_chunk = [&](int c, int8_t* buf) {
@@ -174,7 +152,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void conv_bband_kernel(BBandArgs a
 #ifdef TF2_CHECK_DMA
       dma_stamp(buf + sl * (NP0 * 64) + grp * 1024);
 #endif
-      bb_dma16(src, buf + sl * (NP0 * 64) + grp * 1024);
+      dma16_hidden(src, buf + sl * (NP0 * 64) + grp * 1024);
     }
   };
   issue_chunk(0, ring0);
@@ -254,14 +232,14 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void conv_bband_kernel(BBandArgs a
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                          // pad fill, chunks 0 and 1, headers: complete in every wave
   asm volatile("" ::: "memory");
-  BB_STAMP(1);
+  TF2_BLOCK_STAMP(dbg, 1);
 
   // ---- phase 0: reduce over the halo band ----------------------------------------------------------------------------------
   int bm0[J0];                                           // per-lane B address of column tile j inside a [pixel][64] slab
 #pragma unroll
   for (int j = 0; j < J0; j++) {
     const int row = (wn + j * WN) * 32 + (lane & 31);
-    bm0[j] = row * 64 + ((half ^ ((row >> 2) & 3)) << 4);
+    bm0[j] = swz_off(row, half);
   }
   using Sched = BbSched<KS1, SC, MT, DUAL1>;
   auto step0 = [&](auto v_c) {
@@ -307,7 +285,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void conv_bband_kernel(BBandArgs a
     }
     __builtin_amdgcn_sched_barrier(0);
   };
-  bb_static_for<0, KS1>(step0);
+  static_for<0, KS1>(step0);
   // Horner step of a two-window layer: acc = (acc << dshift[1][row]) [+ the low window's sums]; dshift sits behind rows | lo
   auto window_combine = [&](const int8_t* hdr, int tms, int hst, int nj, bool add_low) __attribute__((always_inline)) {
 #pragma unroll
@@ -331,7 +309,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void conv_bband_kernel(BBandArgs a
     }
   };
   if constexpr (DUAL1) window_combine(hdr1, tms1, hst1, J0, true);
-  BB_STAMP(2);
+  TF2_BLOCK_STAMP(dbg, 2);
 
   // hand-over: requantise (pe.cl:185-203, relu.cl:54) into the halo tile; pixels of rows outside the image keep the pad value
   {
@@ -376,7 +354,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void conv_bband_kernel(BBandArgs a
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                          // the halo tile is complete
   asm volatile("" ::: "memory");
-  BB_STAMP(3);
+  TF2_BLOCK_STAMP(dbg, 3);
 
   // ---- phase 1: the 3x3 over the halo tile; step e = (tap t, slab s) -----------------------------------------------------------
   int h0[J1];
@@ -409,8 +387,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void conv_bband_kernel(BBandArgs a
     }
     __builtin_amdgcn_sched_barrier(0);
   };
-  bb_static_for<0, N1>(step1);
-  BB_STAMP(4);
+  static_for<0, N1>(step1);
+  TF2_BLOCK_STAMP(dbg, 4);
 
   // residual tiles of pass q (16 contiguous NHWC bytes per lane and column tile), loaded one pass ahead
   auto load_res = [&](i32x4 (&rv)[MT][J1], int q) __attribute__((always_inline)) {
@@ -454,7 +432,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void conv_bband_kernel(BBandArgs a
           const i32x4 out = outs[j];
           const int row = (wn + j * WN) * 32 + (lane & 31);
           const int c = (chl & 63) >> 4;
-          *reinterpret_cast<i32x4*>(mid2 + (chl >> 6) * (NP1 * 64) + row * 64 + ((c ^ ((row >> 2) & 3)) << 4)) = out;
+          *reinterpret_cast<i32x4*>(swz_at(mid2 + (chl >> 6) * (NP1 * 64), row, c)) = out;
           if (a.keep_mid && row < n_px)
             *reinterpret_cast<i32x4*>(a.mid2 + (size_t)(pix_base + row) * M + chl) = out;
         }
@@ -466,14 +444,14 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void conv_bband_kernel(BBandArgs a
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                          // the expand's B tile is complete (every wave wrote its channels)
   asm volatile("" ::: "memory");
-  BB_STAMP(5);
+  TF2_BLOCK_STAMP(dbg, 5);
 
   // ---- phase 2: C / M passes of the 1x1 expand over the B tile ------------------------------------------------------------------
   int bm1[J1];
 #pragma unroll
   for (int j = 0; j < J1; j++) {
     const int row = (wn + j * WN) * 32 + (lane & 31);
-    bm1[j] = row * 64 + ((half ^ ((row >> 2) & 3)) << 4);
+    bm1[j] = TF2_SWZ_OFF(row, half);          // (the macro form: lds_tile.h)
   }
   const int lo_b3 = a.relu3 ? 0 : -128;
   const int rlo = a.add_relu ? 0 : -128;
@@ -543,10 +521,9 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void conv_bband_kernel(BBandArgs a
       }
       __builtin_amdgcn_sched_barrier(0);
     };
-    bb_static_for<0, 2 * KS2>(step2);
+    static_for<0, 2 * KS2>(step2);
   }
-  BB_STAMP(6);
-#undef BB_STAMP
+  TF2_BLOCK_STAMP(dbg, 6);
 #undef BB_BUF
 #undef BB_BUFL
 }

@@ -32,19 +32,9 @@
 #include "tf2_internal.h"
 #include "tf2_device.h"
 #include "requant_epilogue.h"
+#include "lds_tile.h"
 
 namespace tf2 {
-
-using i32x4 = int __attribute__((ext_vector_type(4)));
-using i32x16 = int __attribute__((ext_vector_type(16)));
-
-#define TF2_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define TF2_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
-
-template <int T, int N, class F>
-__device__ __forceinline__ void bf_static_for(F& fn) {
-  if constexpr (T < N) { fn(std::integral_constant<int, T>{}); bf_static_for<T + 1, N>(fn); }
-}
 
 namespace {
 constexpr int kBfHW = 56, kBfR = 4, kBfLead = 8;
@@ -80,16 +70,11 @@ __global__ __launch_bounds__(512, 4) void conv_bfirst_kernel(BGroupArgs a) {
   const int wm = wave >> 2, wn = wave & 3;               // 2 x 4 waves: 32 channels x (column tiles wn, wn + 4, ..)
   const int half = lane >> 5;
   const int frow = lane & 31;
-  const int fr0 = frow * 64 + ((half ^ ((frow >> 2) & 3)) << 4);        // a lane's fragment of pixel frow of a [32][64] tile, K half 0
+  const int fr0 = swz_off(frow, half);        // a lane's fragment of pixel frow of a [32][64] tile, K half 0
   const i32x4 nores = {0, 0, 0, 0};
 
   // XCD-aware remap: neighbouring bands of one image (they share halo rows of the input) on one XCD
-  int bid = blockIdx.x;
-  {
-    const int nblk = gridDim.x;
-    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, within = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
-  }
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   constexpr int TPI = HW / R;                            // 14 bands per image
   const int img = bid / TPI;
   const int r0 = (bid - img * TPI) * R;
@@ -97,20 +82,18 @@ __global__ __launch_bounds__(512, 4) void conv_bfirst_kernel(BGroupArgs a) {
   const size_t px_band = px_img + (size_t)r0 * HW;
 
   long long* const dbg = a.dbg ? a.dbg + (size_t)blockIdx.x * 16 : nullptr;       // tools/block timelines: 100 MHz wall clock per phase
-#define BF_STAMP(i) do { if (dbg && tid == 0) dbg[i] = (long long)wall_clock64(); } while (0)
-  BF_STAMP(0);
+  TF2_BLOCK_STAMP(dbg, 0);
   // (side job: this step's -128 flags of the input preparation -- PrepArgs::q128, read by conv_stem_pool_kernel, the launch in front of this
   //  one -- are cleared for the next step: BGroupArgs::ctr carries them here, B words)
   if (a.ctr && blockIdx.x == 0 && tid < a.B) a.ctr[tid] = 0u;
 
   // ---- prologue ---------------------------------------------------------------------------------------------------------------
-  // LDS-DMA: lane l of an instruction fills pixel row l >> 2, 16-byte slot l & 3 of a 16-pixel group; with the XOR swizzle slot c'
-  // of pixel h holds chunk c' ^ ((h >> 2) & 3)
+  // LDS-DMA: what this lane fetches of a 16-pixel group of a swizzled [pixel][64] tile (lds_tile.h)
   {
-    const int chunk = (lane & 3) ^ ((lane >> 4) & 3), drow = lane >> 2;
+    const int chunk = dma_lane_chunk(lane), drow = dma_lane_row(lane);
     // (1) the halo tile filled with the stored form of x = 0 (the 3x3's pad row)
     for (int gi = wave; gi < NHALO / 16; gi += 8)
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(a.zero2 + chunk * 16), TF2_LDS_PTR(halo + gi * 1024), 16, 0, 0);
+      lds_dma16(a.zero2 + chunk * 16, halo + gi * 1024);
     // (2) the band's input: LDS pixel q = LEAD + halo-band pixel (row r0 - 1 first)
     for (int gi = wave; gi < NT0 * 2; gi += 8) {
       const int hp = gi * 16 + drow - LEAD;
@@ -118,7 +101,7 @@ __global__ __launch_bounds__(512, 4) void conv_bfirst_kernel(BGroupArgs a) {
       const int row = r0 - 1 + hr;
       const bool ok = hp >= 0 && hp < NHP && (unsigned)row < (unsigned)HW;
       const int8_t* src = ok ? a.x + (px_img + (size_t)(row * HW + (hp - hr * HW))) * 64 + chunk * 16 : a.zero + chunk * 16;
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(xt + gi * 1024), 16, 0, 0);
+      lds_dma16(src, xt + gi * 1024);
     }
     // (3) header images (rows {bias | dbl, alpha, addend64} | lo | dshift per m-tile), exactly their used bytes
     auto hdr_copy = [&](const int32_t* hdr, int hdr_stride, int n_mt, int bytes, int8_t* dst) {
@@ -182,7 +165,7 @@ __global__ __launch_bounds__(512, 4) void conv_bfirst_kernel(BGroupArgs a) {
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                          // pad fill, input tiles, headers: complete in every wave
   asm volatile("" ::: "memory");
-  BF_STAMP(1);
+  TF2_BLOCK_STAMP(dbg, 1);
 
   // ---- phase 1: reduce (1x1, 64 -> 64, K = one slab) over the band and its halo rows -> the 3x3's halo tile ---------------------
   Afr1 f0, f1;                                           // the 3x3's fragments, one step ahead
@@ -217,7 +200,7 @@ __global__ __launch_bounds__(512, 4) void conv_bfirst_kernel(BGroupArgs a) {
       const int row = r0 - 1 + hr;
       if (hp >= 0 && hp < NHP && (unsigned)row < (unsigned)HW) {
         const int h = hr * Wp + col + 1;
-        *reinterpret_cast<i32x4*>(halo + h * 64 + (((chl >> 4) ^ ((h >> 2) & 3)) << 4)) = out;
+        *reinterpret_cast<i32x4*>(swz_at(halo, h, chl >> 4)) = out;
         if (a.keep_s && hr >= 1 && hr <= R)
           *reinterpret_cast<i32x4*>(a.mid1 + (px_img + (size_t)(row * HW + col)) * 64 + chl) = out;
       }
@@ -226,7 +209,7 @@ __global__ __launch_bounds__(512, 4) void conv_bfirst_kernel(BGroupArgs a) {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                          // the halo tile is complete
   asm volatile("" ::: "memory");
-  BF_STAMP(2);
+  TF2_BLOCK_STAMP(dbg, 2);
 
   // ---- phase 2: the 3x3 over the halo tile (step = tap; a tap is the tile at a shifted pixel address) -> the expand's B tile --------
   i32x16 acc[2];
@@ -252,7 +235,7 @@ __global__ __launch_bounds__(512, 4) void conv_bfirst_kernel(BGroupArgs a) {
 #pragma unroll
       for (int j = 0; j < 2; j++) {
         const int h = h0[j] + (t / 3) * Wp + t % 3;
-        ba[j] = h * 64 + ((half ^ ((h >> 2) & 3)) << 4);
+        ba[j] = swz_off(h, half);
       }
 #pragma unroll
       for (int ks = 0; ks < 2; ks++) {
@@ -264,9 +247,9 @@ __global__ __launch_bounds__(512, 4) void conv_bfirst_kernel(BGroupArgs a) {
       }
       __builtin_amdgcn_sched_barrier(0);                 // steps stay in order: the unrolled loop must not pile up loads
     };
-    bf_static_for<0, 9>(step);
+    static_for<0, 9>(step);
   }
-  BF_STAMP(3);
+  TF2_BLOCK_STAMP(dbg, 3);
   {
     const int* const prm2 = reinterpret_cast<const int*>(hdr2);
     const int lo_b = a.relu2 ? 0 : -128;
@@ -286,7 +269,7 @@ __global__ __launch_bounds__(512, 4) void conv_bfirst_kernel(BGroupArgs a) {
       for (int j = 0; j < 2; j++) {
         const int p = (wn * 2 + j) * 32 + frow;
         if (wn * 2 + j < NT1)                              // (the wave grid's eighth column tile holds no pixel)
-          *reinterpret_cast<i32x4*>(mid2 + (wn * 2 + j) * 2048 + frow * 64 + (((chl >> 4) ^ ((frow >> 2) & 3)) << 4)) = outs[j];
+          *reinterpret_cast<i32x4*>(swz_at(mid2 + (wn * 2 + j) * 2048, frow, chl >> 4)) = outs[j];
         if (a.keep_s && p < NPB) *reinterpret_cast<i32x4*>(a.mid2 + (px_band + p) * 64 + chl) = outs[j];
       }
     };
@@ -295,7 +278,7 @@ __global__ __launch_bounds__(512, 4) void conv_bfirst_kernel(BGroupArgs a) {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                          // the expand's B tile is complete
   asm volatile("" ::: "memory");
-  BF_STAMP(4);
+  TF2_BLOCK_STAMP(dbg, 4);
 
   // ---- phase 3: shortcut tile -> residual, expand + residual -> y -------------------------------------------------------------------
   // Wave w owns output channels [32 w, 32 w + 32) -- its expand and shortcut fragments stay in registers for the whole phase -- and sweeps
@@ -404,8 +387,7 @@ __global__ __launch_bounds__(512, 4) void conv_bfirst_kernel(BGroupArgs a) {
     for (int t0 = 0; t0 < 6; t0 += 2) tiles(std::integral_constant<int, 2>{}, t0);
     tiles(std::integral_constant<int, 1>{}, 6);
   }
-  BF_STAMP(5);
-#undef BF_STAMP
+  TF2_BLOCK_STAMP(dbg, 5);
 }
 
 // Rows this kernel is instantiated for: what Net::bgroup_first_at admits (56 x 56 maps, 64 -> 256 | 64 -> 64 -> 64 -> 256, dense

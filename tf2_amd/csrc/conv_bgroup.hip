@@ -31,32 +31,12 @@
 #include "tf2_internal.h"
 #include "tf2_device.h"
 #include "requant_epilogue.h"
+#include "lds_tile.h"
 
 namespace tf2 {
 
-using i32x4 = int __attribute__((ext_vector_type(4)));
-using i32x16 = int __attribute__((ext_vector_type(16)));
-
-#define TF2_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define TF2_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
-
-template <int T, int N, class F>
-__device__ __forceinline__ void bg_static_for(F& fn) {
-  if constexpr (T < N) { fn(std::integral_constant<int, T>{}); bg_static_for<T + 1, N>(fn); }
-}
-
 constexpr int kBgMembers = 8;
 constexpr int kBgHdrSlot = 2048;             // LDS bytes reserved per header image (rows | lo of one m-tile)
-
-template <int N>
-__device__ __forceinline__ void bg_wait_vmcnt() {
-  static_assert(N == 0 || N == 2 || N == 4 || N == 6 || N == 8, "prepared immediates");
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-}
 
 // The eight members of an image meet at eight flag words.  A flag is (epoch << 8) | XCC id of the member: the epoch is a word of the
 // workspace that the step's first kernel increments, so flags need no zeroing and a stale copy of a flag line (an older
@@ -185,18 +165,17 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup_kernel(BGroupChain c) {
   int tid_ = threadIdx.x;
   asm volatile("" : "+v"(tid_));
   const int tid = tid_, lane = tid & 63, half = lane >> 5;
-  // LDS-DMA: lane l fills row l >> 2, slot l & 3, which holds chunk slot ^ ((row >> 2) & 3)
-  const int chunk = (lane & 3) ^ ((lane >> 4) & 3), drow = lane >> 2;
+  // LDS-DMA: what this lane fetches of a 16-row group of a swizzled [row][64] tile (lds_tile.h)
+  const int chunk = TF2_DMA_LANE_CHUNK(lane), drow = TF2_DMA_LANE_ROW(lane);
   const int p_lane = 32 * t + (lane & 31);               // the pixel of this lane's MFMA column
   const bool p_ok = worker && p_lane < NPX;
   // fragment address inside a [32 rows][64 bytes] swizzled tile: row = lane & 31, chunk c = 2 * ks + half
   const int frow = lane & 31;
-  const int fr0 = frow * 64 + (((0 + half) ^ ((frow >> 2) & 3)) << 4);      // ks = 0; ks = 1 is the same address ^ 32
+  const int fr0 = TF2_SWZ_OFF(frow, half);      // ks = 0; ks = 1 is the same address ^ 32
   unsigned* const ctr = a.ctr + (size_t)img * 32;         // three rows of eight flags: roll call (kb > 0: "input complete"), two meetings
 
   long long* const dbg = (a.dbg && kb == 0) ? a.dbg + (size_t)blockIdx.x * 16 : nullptr;       // tools/bgroup_timeline.py: 100 MHz wall clock per phase
-#define BG_STAMP(i) do { if (dbg && tid == 0) dbg[i] = (long long)wall_clock64(); } while (0)
-  BG_STAMP(0);
+  TF2_BLOCK_STAMP(dbg, 0);
 
   // member's rows inside the packed tiles (TM = 64 or 128 rows per m-tile; dense layers: entry = m-tile * nslab + slab)
   const int c1 = 32 * m;                                 // first output channel of this member in reduce / 3x3
@@ -208,7 +187,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup_kernel(BGroupChain c) {
   auto w_dma = [&](const int8_t* w, int tm, int entry, int ro, int8_t* dst) {
 #pragma unroll
     for (int g2 = 0; g2 < 2; g2++)
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(w + ((size_t)entry * tm + ro + 16 * g2 + drow) * 64 + chunk * 16), TF2_LDS_PTR(dst + g2 * 1024), 16, 0, 0);
+      lds_dma16(w + ((size_t)entry * tm + ro + 16 * g2 + drow) * 64 + chunk * 16, dst + g2 * 1024);
   };
 
   // ---- kernel start: headers (rows {bias | dbl, alpha, addend64} and lo of the member's m-tiles), the reduce's weights ----
@@ -217,7 +196,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup_kernel(BGroupChain c) {
       const int used = ((kPrmWordsPerRow * tm * 4) + 1023) & ~1023;
       const int8_t* src = reinterpret_cast<const int8_t*>(hdr) + (size_t)mt * hdr_bytes + lane * 16;
       for (int i = wave; i * 1024 < used; i += 8)
-        __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src + i * 1024), TF2_LDS_PTR(hdr_lds + slot * kBgHdrSlot + i * 1024), 16, 0, 0);
+        lds_dma16(src + i * 1024, hdr_lds + slot * kBgHdrSlot + i * 1024);
     };
     hdr_dma(a.hdr1, a.hdr1_bytes, mt1, a.tm1, 0);
     hdr_dma(a.hdr2, a.hdr2_bytes, mt2, a.tm2, 1);
@@ -248,9 +227,9 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup_kernel(BGroupChain c) {
         const int p = 32 * t + 16 * g2 + drow;
         const int8_t* src = p < NPX ? a.x + (px_img + p) * C + s * 64 + chunk * 16 : a.zero + chunk * 16;
         int8_t* const dst = ring + slot * STAGE + g2 * 1024;
-        if (kb == 0) __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(dst), 16, 0, 0);                // written before this launch
-        else if (local_in) __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(dst), 16, 0, 1);        // by this group, in this XCD's L2
-        else __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(dst), 16, 0, 16);
+        if (kb == 0) lds_dma16(src, dst);                // written before this launch
+        else if (local_in) lds_dma16_aux(src, dst, 1);        // by this group, in this XCD's L2
+        else lds_dma16_aux(src, dst, 16);
       }
     };
     if (worker) {
@@ -259,7 +238,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup_kernel(BGroupChain c) {
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                                       // headers and the reduce's weights are in LDS (pieces fetched by every wave)
-    BG_STAMP(1);
+    TF2_BLOCK_STAMP(dbg, 1);
     if (kb == 0) {
       if (ctl[5] == (int)blockIdx.x + 1) return;            // (test-only: this member leaves its group; the others report and go on)
       tag = ((unsigned)ctl[0] << 8) | (xcc & 0xff);        // (the epoch word was stored before the barrier)
@@ -273,7 +252,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup_kernel(BGroupChain c) {
       int cs = 0, is = S - 1;
       for (int s = 0; s < KS1; s++) {
         // stages 0 .. S-2 landed above; later: S-2 younger stages (2 DMAs each) may fly while they have been issued
-        if (s >= S - 1) { if (s + S - 2 < KS1) bg_wait_vmcnt<2 * (S - 2)>(); else bg_wait_vmcnt<0>(); }
+        if (s >= S - 1) { if (s + S - 2 < KS1) vm_wait<2 * (S - 2)>(); else vm_wait<0>(); }
         const int8_t* A = work + s * 2048;
         const int8_t* B = ring + cs * STAGE;
         const i32x4 a0 = *reinterpret_cast<const i32x4*>(A + fr0), a1 = *reinterpret_cast<const i32x4*>(A + (fr0 ^ 32));
@@ -285,7 +264,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup_kernel(BGroupChain c) {
       }
 #pragma unroll
       for (int r = 0; r < 16; r++) acc[r] += acc1[r];
-      BG_STAMP(2);
+      TF2_BLOCK_STAMP(dbg, 2);
       if (kb == 0) local0 = bg_rollcall_wave(ctr, tag, lane, a.epoch, ctl[4], 0x01u);
       // requantise, write this member's 32 channels of mid1 (the other members read them next)
       int a16[16];
@@ -302,11 +281,11 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup_kernel(BGroupChain c) {
     }
   }
   bg_signal(ctr + 8, m, tag, tid);
-  BG_STAMP(3);
+  TF2_BLOCK_STAMP(dbg, 3);
   // the 3x3's weights (this member's 32 rows of all 9 x KS2 steps) on their way while the group gathers
   for (int e = wave; e < NE; e += 8) w_dma(a.w2, a.tm2, mt2 * NE + e, ro2, wreg + e * 2048);
   const int r_m1 = bg_wait(ctr + 8, tag, tid, ctl + 1, a.epoch, ctl[4], 0x20u | ((unsigned)kb << 8)); if (r_m1 < 0) return; const bool local1 = r_m1 > 0;
-  BG_STAMP(4);
+  TF2_BLOCK_STAMP(dbg, 4);
 
   // =================================== phase B: 3x3 / pad 1, M -> M ===================================
   {
@@ -318,12 +297,12 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup_kernel(BGroupChain c) {
       const bool ok = (unsigned)row < (unsigned)HW && (unsigned)col < (unsigned)HW;
       const int8_t* src = ok ? a.mid1 + (px_img + row * HW + col) * M + s * 64 + chunk * 16
                              : a.zero2 + s * 64 + chunk * 16;       // the 3x3's pad row: the stored form of x = 0
-      if (local1) __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(halo + s * HALO + grp * 1024), 16, 0, 1);       // this XCD's L2
-      else __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(halo + s * HALO + grp * 1024), 16, 0, 16);            // memory side
+      if (local1) lds_dma16_aux(src, halo + s * HALO + grp * 1024, 1);       // this XCD's L2
+      else lds_dma16_aux(src, halo + s * HALO + grp * 1024, 16);            // memory side
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                                       // halo and weights complete in every wave
-    BG_STAMP(5);
+    TF2_BLOCK_STAMP(dbg, 5);
     if (worker) {
       const int pq = p_ok ? p_lane : 0;                    // lanes beyond the map compute on pixel 0 and are never stored
       const int oh = pq / HW, ow = pq - oh * HW;
@@ -336,16 +315,16 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup_kernel(BGroupChain c) {
         constexpr int tap = e / KS2, s = e % KS2;
         const int8_t* A = wreg + e * 2048;
         const int h = h0 + (tap / 3) * 16 + tap % 3;
-        const int ba = s * HALO + h * 64 + ((half ^ ((h >> 2) & 3)) << 4);
+        const int ba = TF2_SWZ_AT(s * HALO, h, half);
         const i32x4 a0 = *reinterpret_cast<const i32x4*>(A + fr0), a1 = *reinterpret_cast<const i32x4*>(A + (fr0 ^ 32));
         const i32x4 b0 = *reinterpret_cast<const i32x4*>(halo + ba), b1 = *reinterpret_cast<const i32x4*>(halo + (ba ^ 32));
         acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b0, acc, 0, 0, 0);
         acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b1, acc1, 0, 0, 0);
       };
-      bg_static_for<0, NE>(step);
+      static_for<0, NE>(step);
 #pragma unroll
       for (int r = 0; r < 16; r++) acc[r] += acc1[r];
-      BG_STAMP(6);
+      TF2_BLOCK_STAMP(dbg, 6);
       int a16[16];
 #pragma unroll
       for (int r = 0; r < 16; r++) a16[r] = acc[r];
@@ -360,7 +339,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup_kernel(BGroupChain c) {
     }
   }
   bg_signal(ctr + 16, m, tag, tid);
-  BG_STAMP(7);
+  TF2_BLOCK_STAMP(dbg, 7);
   // the expand's weights: [32-row tile][slab] of this member's C / 8 rows, into the 3x3's weight region
   for (int u = wave; u < CT * KS2; u += 8) {
     const int ch = c3 + 32 * (u / KS2);
@@ -375,7 +354,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup_kernel(BGroupChain c) {
     rv[q] = *reinterpret_cast<const i32x4*>(rp);
   }
   const int r_m2 = bg_wait(ctr + 16, tag, tid, ctl + 2, a.epoch, ctl[4], 0x30u | ((unsigned)kb << 8)); if (r_m2 < 0) return; const bool local2 = r_m2 > 0;
-  BG_STAMP(8);
+  TF2_BLOCK_STAMP(dbg, 8);
 
   // =================================== phase C: expand, 1x1 M -> C, + residual ===================================
   {
@@ -387,13 +366,13 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup_kernel(BGroupChain c) {
         for (int g2 = 0; g2 < 2; g2++) {
           const int p = 32 * t + 16 * g2 + drow;
           const int8_t* src = p < NPX ? a.mid2 + (px_img + p) * M + s * 64 + chunk * 16 : a.zero + chunk * 16;
-          if (local2) __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(tile + s * 2048 + g2 * 1024), 16, 0, 1);
-          else __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(tile + s * 2048 + g2 * 1024), 16, 0, 16);
+          if (local2) lds_dma16_aux(src, tile + s * 2048 + g2 * 1024, 1);
+          else lds_dma16_aux(src, tile + s * 2048 + g2 * 1024, 16);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                                       // the expand's weights (fetched by every wave) and this wave's pixel tile
-    BG_STAMP(9);
+    TF2_BLOCK_STAMP(dbg, 9);
     if (worker) {
       const int lo_b = a.relu3 ? 0 : -128, rlo = a.add_relu ? 0 : -128;
       static_assert(CT % 2 == 0, "the expand is swept two 32-row tiles at a time");
@@ -438,8 +417,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup_kernel(BGroupChain c) {
       }
     }
   }
-  BG_STAMP(10);
-#undef BG_STAMP
+  TF2_BLOCK_STAMP(dbg, 10);
   // every store of this member acknowledged and every wave done with the LDS regions, then its flag at the next bottleneck's roll call
   if (kb + 1 < c.n) bg_signal(c.b[kb + 1].ctr + (size_t)img * 32, m, tag, tid);
   }
@@ -473,25 +451,25 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup56f_kernel(BGroupArgs a) {
   const int half = lane >> 5;
   const int img = a.img0 + ((int)blockIdx.x & 7) + 8 * ((int)blockIdx.x >> 6), m = ((int)blockIdx.x >> 3) & 7;
   if (img >= a.B) return;
-  const int chunk = (lane & 3) ^ ((lane >> 4) & 3);
-  const int drow = lane >> 2;
+  const int chunk = TF2_DMA_LANE_CHUNK(lane);
+  const int drow = TF2_DMA_LANE_ROW(lane);
   const size_t px_img = (size_t)img * NPX;
   const size_t px_band = px_img + (size_t)m * NPB;
   unsigned* const ctr = a.ctr + (size_t)img * 32;
   const int frow = lane & 31;
-  const int fr0 = frow * 64 + ((half ^ ((frow >> 2) & 3)) << 4);
+  const int fr0 = TF2_SWZ_OFF(frow, half);
   const i32x4 nores = {0, 0, 0, 0};
 
   auto w_dma = [&](const int8_t* w, size_t row0, int8_t* dst) {
 #pragma unroll
     for (int g2 = 0; g2 < 2; g2++)
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(w + (row0 + 16 * g2 + drow) * 64 + chunk * 16), TF2_LDS_PTR(dst + g2 * 1024), 16, 0, 0);
+      lds_dma16(w + (row0 + 16 * g2 + drow) * 64 + chunk * 16, dst + g2 * 1024);
   };
   {
     auto hdr_dma = [&](const int32_t* hdr, int hdr_bytes, int mt, int slot) {
       const int8_t* src = reinterpret_cast<const int8_t*>(hdr) + (size_t)mt * hdr_bytes + lane * 16;
       for (int i = wave; i < kBgHdrSlot / 1024; i += 8)
-        __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src + i * 1024), TF2_LDS_PTR(hdr_lds + slot * kBgHdrSlot + i * 1024), 16, 0, 0);
+        lds_dma16(src + i * 1024, hdr_lds + slot * kBgHdrSlot + i * 1024);
     };
     hdr_dma(a.hdr1, a.hdr1_bytes, 0, 0);
     hdr_dma(a.hdr2, a.hdr2_bytes, 0, 1);
@@ -502,8 +480,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup56f_kernel(BGroupArgs a) {
       const int n_mt = 256 / a.tms, per = (4 * kBgHdrSlot / n_mt) >> 10;       // KiB pieces per m-tile
       for (int i = wave; i < n_mt * per; i += 8) {
         const int mt = i / per, kk = i - mt * per;
-        __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(reinterpret_cast<const int8_t*>(a.hdrs) + (size_t)mt * a.hdrs_bytes + kk * 1024 + lane * 16),
-                                         TF2_LDS_PTR(hdr_lds + 6 * kBgHdrSlot + i * 1024), 16, 0, 0);
+        lds_dma16(reinterpret_cast<const int8_t*>(a.hdrs) + (size_t)mt * a.hdrs_bytes + kk * 1024 + lane * 16, hdr_lds + 6 * kBgHdrSlot + i * 1024);
       }
     }
     for (int u = wave; u < NWN * 2; u += 8) w_dma(a.w1, (size_t)(u >> 1) * 64 + 32 * (u & 1), wreg + u * 2048);      // reduce: [window][two 32-row tiles]
@@ -511,7 +488,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup56f_kernel(BGroupArgs a) {
     for (int gi = wave; gi < NT * 2; gi += 8) {
       const int p = 16 * gi + drow;
       const int8_t* src = p < NPB ? a.x + (px_band + p) * CIN + chunk * 16 : a.zero + chunk * 16;
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(xt + gi * 1024), 16, 0, 0);
+      lds_dma16(src, xt + gi * 1024);
     }
     if (tid == 64 * 7) {
       i32x4 e;                                             // control words {step counter, error word, poll limit, test: withheld block + 1}
@@ -590,8 +567,8 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup56f_kernel(BGroupArgs a) {
       const int row = m * PR - 1 + (h >> 6), col = (h & 63) - 1;
       const bool ok = (unsigned)row < (unsigned)HW && (unsigned)col < (unsigned)HW;
       const int8_t* src = ok ? a.mid1 + (px_img + row * HW + col) * M + chunk * 16 : a.zero2 + chunk * 16;
-      if (local1) __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(halo + grp * 1024), 16, 0, 1);
-      else __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(halo + grp * 1024), 16, 0, 16);
+      if (local1) lds_dma16_aux(src, halo + grp * 1024, 1);
+      else lds_dma16_aux(src, halo + grp * 1024, 16);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -614,7 +591,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup56f_kernel(BGroupArgs a) {
         for (int tap = 0; tap < 9; tap++) {
           const int8_t* A = wreg + tap * 4096;
           const int h = h0 + (tap / 3) * HC + tap % 3;
-          const int ba = h * 64 + ((half ^ ((h >> 2) & 3)) << 4);
+          const int ba = TF2_SWZ_OFF(h, half);
           const i32x4 b0 = *reinterpret_cast<const i32x4*>(halo + ba), b1 = *reinterpret_cast<const i32x4*>(halo + (ba ^ 32));
           acc[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(*reinterpret_cast<const i32x4*>(A + fr0), b0, acc[0], 0, 0, 0);
           acc[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(*reinterpret_cast<const i32x4*>(A + 2048 + fr0), b0, acc[1], 0, 0, 0);
@@ -630,7 +607,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup56f_kernel(BGroupArgs a) {
           if (a.fast2 == 1) out = requant_tile16<false, 0, true>(a16, prm2, 64, 32 * q + 4 * half, lo_b, -128, nores, a.dbl2 != 0, false);
           else out = requant_tile16<false, 0, false>(a16, prm2, 64, 32 * q + 4 * half, lo_b, -128, nores, a.dbl2 != 0, a.fast2 == 2);
           const int row = lane & 31, c = 2 * q + half;
-          *reinterpret_cast<i32x4*>(tiles + t * 2048 + row * 64 + ((c ^ ((row >> 2) & 3)) << 4)) = out;
+          *reinterpret_cast<i32x4*>(TF2_SWZ_AT(tiles + t * 2048, row, c)) = out;
           if (ok) *reinterpret_cast<i32x4*>(a.mid2 + (px_band + 32 * t + row) * M + 32 * q + 16 * half) = out;
         }
       }
@@ -748,15 +725,14 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup28_kernel(BGroupChain c) { 
   int tid_ = threadIdx.x;
   asm volatile("" : "+v"(tid_));
   const int tid = tid_, lane = tid & 63, half = lane >> 5;
-  const int chunk = (lane & 3) ^ ((lane >> 4) & 3), drow = lane >> 2;
+  const int chunk = TF2_DMA_LANE_CHUNK(lane), drow = TF2_DMA_LANE_ROW(lane);
   const int frow = lane & 31;
-  const int fr0 = frow * 64 + ((half ^ ((frow >> 2) & 3)) << 4);
+  const int fr0 = TF2_SWZ_OFF(frow, half);
   const int p_lane = 32 * t + (lane & 31);               // pixel of this lane's column inside the band (phases A, B)
   const bool p_ok = worker && p_lane < NPB;
   unsigned* const ctr = a.ctr + (size_t)img * 32;
   long long* const dbg = (a.dbg && kb == 0) ? a.dbg + (size_t)blockIdx.x * 16 : nullptr;       // tools/bgroup_timeline.py
-#define BG_STAMP(i) do { if (dbg && tid == 0) dbg[i] = (long long)wall_clock64(); } while (0)
-  BG_STAMP(0);
+  TF2_BLOCK_STAMP(dbg, 0);
   const int c1 = 64 * cm;                                // first intermediate channel of this member
   const int mt1 = c1 / a.tm1, ro1 = c1 % a.tm1;
   const int mt2 = c1 / a.tm2, ro2 = c1 % a.tm2;
@@ -765,14 +741,14 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup28_kernel(BGroupChain c) { 
   auto w_dma = [&](const int8_t* w, size_t row0, int8_t* dst) {        // 32 rows x 64 bytes starting at row row0 of the tile storage
 #pragma unroll
     for (int g2 = 0; g2 < 2; g2++)
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(w + (row0 + 16 * g2 + drow) * 64 + chunk * 16), TF2_LDS_PTR(dst + g2 * 1024), 16, 0, 0);
+      lds_dma16(w + (row0 + 16 * g2 + drow) * 64 + chunk * 16, dst + g2 * 1024);
   };
   {
     auto hdr_dma = [&](const int32_t* hdr, int hdr_bytes, int mt, int tm, int nwords, int slot) {
       const int used = (nwords * tm * 4 + 1023) & ~1023;
       const int8_t* src = reinterpret_cast<const int8_t*>(hdr) + (size_t)mt * hdr_bytes + lane * 16;
       for (int i = wave; i * 1024 < used; i += 8)
-        __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src + i * 1024), TF2_LDS_PTR(hdr_lds + slot * kHdrSlot + i * 1024), 16, 0, 0);
+        lds_dma16(src + i * 1024, hdr_lds + slot * kHdrSlot + i * 1024);
     };
     hdr_dma(a.hdr1, a.hdr1_bytes, mt1, a.tm1, kPrmWordsPerRow + 2, 0);
     hdr_dma(a.hdr2, a.hdr2_bytes, mt2, a.tm2, kPrmWordsPerRow + 2, 1);
@@ -823,9 +799,9 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup28_kernel(BGroupChain c) { 
         const int p = 32 * t + 16 * g2 + drow;
         const int8_t* src = p < NPB ? a.x + (px_band + p) * C + s * 64 + chunk * 16 : a.zero + chunk * 16;
         int8_t* const dst = ring + slot * STAGE + g2 * 1024;
-        if (kb == 0) __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(dst), 16, 0, 0);               // written before this launch
-        else if (local_in) __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(dst), 16, 0, 1);       // by this group, in this XCD's L2
-        else __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(dst), 16, 0, 16);
+        if (kb == 0) lds_dma16(src, dst);               // written before this launch
+        else if (local_in) lds_dma16_aux(src, dst, 1);       // by this group, in this XCD's L2
+        else lds_dma16_aux(src, dst, 16);
       }
     };
     if (worker) {
@@ -834,7 +810,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup28_kernel(BGroupChain c) { 
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                                       // headers and the reduce's weights are in LDS
-    BG_STAMP(1);
+    TF2_BLOCK_STAMP(dbg, 1);
     if (kb == 0) {
       if (ctl[5] == (int)blockIdx.x + 1) return;            // (test-only: this member leaves its group; the others report and go on)
       tag = ((unsigned)ctl[0] << 8) | (xcc & 0xff);
@@ -848,7 +824,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup28_kernel(BGroupChain c) { 
     if (worker) {
       int cs = 0, is = S - 1;
       for (int s = 0; s < KS1; s++) {
-        if (s >= S - 1) { if (s + 3 < KS1) bg_wait_vmcnt<6>(); else if (s + 2 < KS1) bg_wait_vmcnt<4>(); else if (s + 1 < KS1) bg_wait_vmcnt<2>(); else bg_wait_vmcnt<0>(); }
+        if (s >= S - 1) { if (s + 3 < KS1) vm_wait<6>(); else if (s + 2 < KS1) vm_wait<4>(); else if (s + 1 < KS1) vm_wait<2>(); else vm_wait<0>(); }
         const int8_t* A = wreg + s * (NW1 * 4096);         // [window][tile q][32 rows][64]
         const int8_t* B = ring + cs * STAGE;
 #pragma unroll
@@ -883,9 +859,9 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup28_kernel(BGroupChain c) { 
       store_mid(acc, prm1, a.tm1, ro1, a.fast1, a.relu1, a.dbl1, a.mid1);
     }
   }
-  BG_STAMP(2);
+  TF2_BLOCK_STAMP(dbg, 2);
   bg_signal(ctr + 8, m, tag, tid);
-  BG_STAMP(3);
+  TF2_BLOCK_STAMP(dbg, 3);
   // the 3x3's weights (of one window): [step e][two 32-row tiles]
   constexpr int NW2 = DUAL2 ? 2 : 1;
   auto load_w2 = [&](int win) {
@@ -894,7 +870,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup28_kernel(BGroupChain c) { 
   };
   load_w2(0);
   const int r_m1 = bg_wait(ctr + 8, tag, tid, ctl + 1, a.epoch, ctl[4], 0x20u | ((unsigned)kb << 8)); if (r_m1 < 0) return; const bool local1 = r_m1 > 0;
-  BG_STAMP(4);
+  TF2_BLOCK_STAMP(dbg, 4);
 
   // =================================== phase B: 3x3 / pad 1, M -> M ===================================
   {
@@ -906,12 +882,12 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup28_kernel(BGroupChain c) { 
       const int row = sp * PR - 1 + (h >> 5), col = (h & 31) - 1;
       const bool ok = (unsigned)row < (unsigned)HW && (unsigned)col < (unsigned)HW;
       const int8_t* src = ok ? a.mid1 + (px_img + row * HW + col) * M + s * 64 + chunk * 16 : a.zero2 + s * 64 + chunk * 16;
-      if (local1) __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(halo + s * HALO + grp * 1024), 16, 0, 1);
-      else __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(halo + s * HALO + grp * 1024), 16, 0, 16);
+      if (local1) lds_dma16_aux(src, halo + s * HALO + grp * 1024, 1);
+      else lds_dma16_aux(src, halo + s * HALO + grp * 1024, 16);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                                       // halo and weights complete in every wave
-    BG_STAMP(5);
+    TF2_BLOCK_STAMP(dbg, 5);
     const int pq = p_ok ? p_lane : 0;
     const int oh = pq / HW, ow = pq - oh * HW;
     const int h0 = oh * HC + ow;
@@ -939,7 +915,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup28_kernel(BGroupChain c) { 
         constexpr int tap = e / KS2, sl = e % KS2;
         const int8_t* A = wreg + e * 4096;
         const int h = h0 + (tap / 3) * HC + tap % 3;
-        const int ba = sl * HALO + h * 64 + ((half ^ ((h >> 2) & 3)) << 4);
+        const int ba = TF2_SWZ_AT(sl * HALO, h, half);
         const i32x4 b0 = *reinterpret_cast<const i32x4*>(halo + ba), b1 = *reinterpret_cast<const i32x4*>(halo + (ba ^ 32));
         const i32x4 a00 = *reinterpret_cast<const i32x4*>(A + fr0), a01 = *reinterpret_cast<const i32x4*>(A + (fr0 ^ 32));
         const i32x4 a10 = *reinterpret_cast<const i32x4*>(A + 2048 + fr0), a11 = *reinterpret_cast<const i32x4*>(A + 2048 + (fr0 ^ 32));
@@ -948,7 +924,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup28_kernel(BGroupChain c) { 
         acc[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a01, b1, acc[0], 0, 0, 0);
         acc[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a11, b1, acc[1], 0, 0, 0);
       };
-      bg_static_for<0, NE>(step);
+      static_for<0, NE>(step);
     }
     }   // windows
     if (worker) {
@@ -967,9 +943,9 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup28_kernel(BGroupChain c) { 
       store_mid(acc, prm2, a.tm2, ro2, a.fast2, a.relu2, a.dbl2, a.mid2);
     }
   }
-  BG_STAMP(6);
+  TF2_BLOCK_STAMP(dbg, 6);
   bg_signal(ctr + 16, m, tag, tid);
-  BG_STAMP(7);
+  TF2_BLOCK_STAMP(dbg, 7);
   // the expand's weights of this wave (32-row tile `wave` of the member's 256 channels): K = 128 -> four fragments, in registers
   const int ch3 = c3 + 32 * wave;
   i32x4 wf[KS2][2];
@@ -982,7 +958,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup28_kernel(BGroupChain c) { 
     }
   }
   const int r_m2 = bg_wait(ctr + 16, tag, tid, ctl + 2, a.epoch, ctl[4], 0x30u | ((unsigned)kb << 8)); if (r_m2 < 0) return; const bool local2 = r_m2 > 0;
-  BG_STAMP(8);
+  TF2_BLOCK_STAMP(dbg, 8);
 
   // =================================== phase C: expand, 1x1 M -> C, + residual ===================================
   {
@@ -991,8 +967,8 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup28_kernel(BGroupChain c) { 
       const int tt = gi / (KS2 * 2), s = (gi >> 1) % KS2, g2 = gi & 1;
       const int p = 32 * tt + 16 * g2 + drow;
       const int8_t* src = p < NPB ? a.mid2 + (px_band + p) * M + s * 64 + chunk * 16 : a.zero + chunk * 16;
-      if (local2) __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(tiles + (tt * KS2 + s) * 2048 + g2 * 1024), 16, 0, 1);
-      else __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(tiles + (tt * KS2 + s) * 2048 + g2 * 1024), 16, 0, 16);
+      if (local2) lds_dma16_aux(src, tiles + (tt * KS2 + s) * 2048 + g2 * 1024, 1);
+      else lds_dma16_aux(src, tiles + (tt * KS2 + s) * 2048 + g2 * 1024, 16);
     }
     const int lo_b = a.relu3 ? 0 : -128, rlo = a.add_relu ? 0 : -128;
     const int mt = ch3 / a.tm3, ro = ch3 % a.tm3;
@@ -1007,14 +983,14 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup28_kernel(BGroupChain c) { 
         const int px = 4 * ci + (lane >> 4), q = (lane & 15) ^ (px & 15);
         const int8_t* src = px < NPB ? a.res + (px_band + px) * a.res_cp + a.res_off + c3 + q * 16 : a.zero;
         // (kb > 0: this block's own output of one bottleneck earlier, stored like exchange data)
-        if (kb == 0) __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(stage + ci * 1024), 16, 0, 0);
-        else if (local2) __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(stage + ci * 1024), 16, 0, 1);
-        else __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(stage + ci * 1024), 16, 0, 16);
+        if (kb == 0) lds_dma16(src, stage + ci * 1024);
+        else if (local2) lds_dma16_aux(src, stage + ci * 1024, 1);
+        else lds_dma16_aux(src, stage + ci * 1024, 16);
       }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                                       // the band's tiles (fetched by every wave)
-    BG_STAMP(9);
+    TF2_BLOCK_STAMP(dbg, 9);
 #pragma unroll
     for (int tt = 0; tt < NT; tt++) {
       const int pxl = 32 * tt + (lane & 31);
@@ -1051,8 +1027,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup28_kernel(BGroupChain c) { 
       if (px < NPB) bg_store_x(a.y + (px_band + px) * a.y_cp + a.y_off + c3 + q * 16, v, local2 || last);      // (an inner output is exchange data)
     }
   }
-  BG_STAMP(10);
-#undef BG_STAMP
+  TF2_BLOCK_STAMP(dbg, 10);
   if (!last) bg_signal(c.b[kb + 1].ctr + (size_t)img * 32, m, tag, tid);      // stores acknowledged, LDS free, then "my output is complete"
   }
 }
@@ -1103,24 +1078,23 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup7_kernel(BGroupChain c) {  
   int tid_ = threadIdx.x;
   asm volatile("" : "+v"(tid_));
   const int tid = tid_, lane = tid & 63, half = lane >> 5;
-  const int chunk = (lane & 3) ^ ((lane >> 4) & 3), drow = lane >> 2;
+  const int chunk = TF2_DMA_LANE_CHUNK(lane), drow = TF2_DMA_LANE_ROW(lane);
   const int frow = lane & 31;
-  const int fr0 = frow * 64 + ((half ^ ((frow >> 2) & 3)) << 4);
+  const int fr0 = TF2_SWZ_OFF(frow, half);
   unsigned* const ctr = a.ctr + (size_t)img * 32;
   long long* const dbg = (a.dbg && kb == 0) ? a.dbg + (size_t)blockIdx.x * 16 : nullptr;       // tools/bgroup_timeline.py
-#define BG_STAMP(i) do { if (dbg && tid == 0) dbg[i] = (long long)wall_clock64(); } while (0)
-  BG_STAMP(0);
+  TF2_BLOCK_STAMP(dbg, 0);
 
   auto w_dma = [&](const int8_t* w, size_t row0, int8_t* dst) {        // 32 rows x 64 bytes starting at tile row row0
 #pragma unroll
     for (int g2 = 0; g2 < 2; g2++)
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(w + (row0 + 16 * g2 + drow) * 64 + chunk * 16), TF2_LDS_PTR(dst + g2 * 1024), 16, 0, 0);
+      lds_dma16(w + (row0 + 16 * g2 + drow) * 64 + chunk * 16, dst + g2 * 1024);
   };
   {
     auto hdr_dma = [&](const int32_t* hdr, int hdr_bytes, int mt, int slot) {
       const int8_t* src = reinterpret_cast<const int8_t*>(hdr) + (size_t)mt * hdr_bytes + lane * 16;
       for (int i = wave; i < kBgHdrSlot / 1024; i += 8)              // rows | lo | dshift of a 64-row m-tile: <= 1792 bytes
-        __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src + i * 1024), TF2_LDS_PTR(hdr_lds + slot * kBgHdrSlot + i * 1024), 16, 0, 0);
+        lds_dma16(src + i * 1024, hdr_lds + slot * kBgHdrSlot + i * 1024);
     };
     hdr_dma(a.hdr1, a.hdr1_bytes, m, 0);
     hdr_dma(a.hdr2, a.hdr2_bytes, m, 1);
@@ -1197,9 +1171,9 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup7_kernel(BGroupChain c) {  
         const int p = 16 * g4 + drow;
         const int8_t* src = p < NPX ? a.x + (px_img + p) * C + (kq * NS + s) * 64 + chunk * 16 : a.zero + chunk * 16;
         int8_t* const dst = st + NW1 * 2048 + g4 * 1024;
-        if (kb == 0) __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(dst), 16, 0, 0);               // written before this launch
-        else if (local_in) __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(dst), 16, 0, 1);       // by this group, in this XCD's L2
-        else __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(dst), 16, 0, 16);
+        if (kb == 0) lds_dma16(src, dst);               // written before this launch
+        else if (local_in) lds_dma16_aux(src, dst, 1);       // by this group, in this XCD's L2
+        else lds_dma16_aux(src, dst, 16);
       }
     };
     // (the header pieces and the step counter of this wave are older in its queue than its ring stages)
@@ -1210,7 +1184,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup7_kernel(BGroupChain c) {  
 #pragma unroll
       for (int r = 0; r < 16; r++) { acc[pt][r] = 0; if (DUAL1) accl[pt][r] = 0; }
     for (int s = 0; s < NS; s++) {
-      if (s + 1 < NS) bg_wait_vmcnt<NI>(); else bg_wait_vmcnt<0>();
+      if (s + 1 < NS) vm_wait<NI>(); else vm_wait<0>();
       const int8_t* A = ring + (s & 1) * STA;
       const int8_t* B = A + NW1 * 2048;
 #pragma unroll
@@ -1229,7 +1203,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup7_kernel(BGroupChain c) {  
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                                       // every wave is done with its ring; headers (fetched by every wave) are in LDS
-    BG_STAMP(1);
+    TF2_BLOCK_STAMP(dbg, 1);
     if (kb == 0) {
       if (ctl[5] == (int)blockIdx.x + 1) return;            // (test-only: this member leaves its group; the others report and go on)
       tag = ((unsigned)ctl[0] << 8) | (xcc & 0xff);
@@ -1253,12 +1227,12 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup7_kernel(BGroupChain c) {  
       if (kb == 0) local0 = bg_rollcall_wave(ctr, tag, lane, a.epoch, ctl[4], 0x01u);
       store_mid(acc, prm1, a.fast1, a.relu1, a.dbl1, a.mid1);
     }
-    BG_STAMP(2);
+    TF2_BLOCK_STAMP(dbg, 2);
   }
   bg_signal(ctr + 8, m, tag, tid);
-  BG_STAMP(3);
+  TF2_BLOCK_STAMP(dbg, 3);
   const int r_m1 = bg_wait(ctr + 8, tag, tid, ctl + 1, a.epoch, ctl[4], 0x20u | ((unsigned)kb << 8)); if (r_m1 < 0) return; const bool local1 = r_m1 > 0;
-  BG_STAMP(4);
+  TF2_BLOCK_STAMP(dbg, 4);
 
   // =================================== phase B: 3x3 / pad 1, M -> M ===================================
   {
@@ -1271,8 +1245,8 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup7_kernel(BGroupChain c) {  
       const int row = hr - 1, col = h - hr * HC - 1;
       const bool ok = (unsigned)row < (unsigned)HW && (unsigned)col < (unsigned)HW;
       const int8_t* src = ok ? a.mid1 + (px_img + row * HW + col) * M + s * 64 + chunk * 16 : a.zero2 + s * 64 + chunk * 16;
-      if (local1) __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(halo + s * HALO + grp * 1024), 16, 0, 1);
-      else __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(halo + s * HALO + grp * 1024), 16, 0, 16);
+      if (local1) lds_dma16_aux(src, halo + s * HALO + grp * 1024, 1);
+      else lds_dma16_aux(src, halo + s * HALO + grp * 1024, 16);
     }
     constexpr int NS = NE / 4, S = 6;                      // 18 steps per K quarter, private ring of 32 weight rows per stage
     int8_t* const ring = wreg + wave * (S * 2048);
@@ -1284,7 +1258,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup7_kernel(BGroupChain c) {  
     for (int s = 0; s < S - 1; s++) issue(s, s);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                                       // halo complete in every wave (and this wave's first stages)
-    BG_STAMP(5);
+    TF2_BLOCK_STAMP(dbg, 5);
     int h0[2];
 #pragma unroll
     for (int pt = 0; pt < 2; pt++) {
@@ -1302,8 +1276,8 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup7_kernel(BGroupChain c) {  
     for (int s = 0; s < NS; s++) {
       // stages 0 .. S-2 landed above; later S-2 younger stages (2 DMAs each) may fly while that many have been issued
       if (s >= S - 1) {
-        if (s + 4 < NS) bg_wait_vmcnt<8>(); else if (s + 3 < NS) bg_wait_vmcnt<6>(); else if (s + 2 < NS) bg_wait_vmcnt<4>();
-        else if (s + 1 < NS) bg_wait_vmcnt<2>(); else bg_wait_vmcnt<0>();
+        if (s + 4 < NS) vm_wait<8>(); else if (s + 3 < NS) vm_wait<6>(); else if (s + 2 < NS) vm_wait<4>();
+        else if (s + 1 < NS) vm_wait<2>(); else vm_wait<0>();
       }
       const int e = kq * NS + s;
       const int tap = e / KS2, sl = e - tap * KS2;
@@ -1314,7 +1288,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup7_kernel(BGroupChain c) {  
 #pragma unroll
       for (int pt = 0; pt < 2; pt++) {
         const int h = h0[pt] + toff;
-        const int ba = sl * HALO + h * 64 + ((half ^ ((h >> 2) & 3)) << 4);
+        const int ba = TF2_SWZ_AT(sl * HALO, h, half);
         b0[pt] = *reinterpret_cast<const i32x4*>(halo + ba); b1[pt] = *reinterpret_cast<const i32x4*>(halo + (ba ^ 32));
       }
       acc[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b0[0], acc[0], 0, 0, 0);      // the two column tiles alternate
@@ -1326,12 +1300,12 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup7_kernel(BGroupChain c) {  
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                                       // rings are dead: the partials may use the region
-    BG_STAMP(6);
+    TF2_BLOCK_STAMP(dbg, 6);
     reduce_quarters(acc, wreg);
     if (kq == 0) store_mid(acc, prm2, a.fast2, a.relu2, a.dbl2, a.mid2);
   }
   bg_signal(ctr + 16, m, tag, tid);
-  BG_STAMP(7);
+  TF2_BLOCK_STAMP(dbg, 7);
   // residual tiles of this wave's 32-row tile of the expand (the bottleneck's input, written before this launch or -- in a
   // chain -- by THIS thread one bottleneck earlier: ordinary loads)
   const int ch3 = (C / kBgMembers) * m + 32 * wave;        // first channel of this wave's tile
@@ -1350,7 +1324,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup7_kernel(BGroupChain c) {  
 #pragma unroll
   for (int s = 0; s < S3 - 1; s++) issue3(s, s);
   const int r_m2 = bg_wait(ctr + 16, tag, tid, ctl + 2, a.epoch, ctl[4], 0x30u | ((unsigned)kb << 8)); if (r_m2 < 0) return; const bool local2 = r_m2 > 0;
-  BG_STAMP(8);
+  TF2_BLOCK_STAMP(dbg, 8);
 
   // =================================== phase C: expand, 1x1 M -> C, + residual (+ global average) ===================================
   {
@@ -1359,12 +1333,12 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup7_kernel(BGroupChain c) {  
       const int s = gi >> 2, g4 = gi & 3;
       const int p = 16 * g4 + drow;
       const int8_t* src = p < NPX ? a.mid2 + (px_img + p) * M + s * 64 + chunk * 16 : a.zero + chunk * 16;
-      if (local2) __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(tiles + s * 4096 + g4 * 1024), 16, 0, 1);
-      else __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(tiles + s * 4096 + g4 * 1024), 16, 0, 16);
+      if (local2) lds_dma16_aux(src, tiles + s * 4096 + g4 * 1024, 1);
+      else lds_dma16_aux(src, tiles + s * 4096 + g4 * 1024, 16);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                                       // the image's tiles (fetched by every wave)
-    BG_STAMP(9);
+    TF2_BLOCK_STAMP(dbg, 9);
     i32x16 acc[2];
 #pragma unroll
     for (int pt = 0; pt < 2; pt++)
@@ -1372,7 +1346,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup7_kernel(BGroupChain c) {  
       for (int r = 0; r < 16; r++) acc[pt][r] = 0;
     int cs = 0, is = S3 - 1;
     for (int s = 0; s < KS2; s++) {
-      if (s >= S3 - 1) { if (s + 2 < KS2) bg_wait_vmcnt<4>(); else if (s + 1 < KS2) bg_wait_vmcnt<2>(); else bg_wait_vmcnt<0>(); }
+      if (s >= S3 - 1) { if (s + 2 < KS2) vm_wait<4>(); else if (s + 1 < KS2) vm_wait<2>(); else vm_wait<0>(); }
       const int8_t* A = ring3 + cs * 2048;
       const i32x4 a0 = *reinterpret_cast<const i32x4*>(A + fr0), a1 = *reinterpret_cast<const i32x4*>(A + (fr0 ^ 32));
       const int8_t* B = tiles + s * 4096;
@@ -1429,8 +1403,7 @@ __global__ __launch_bounds__(512, 2) void conv_bgroup7_kernel(BGroupChain c) {  
       *reinterpret_cast<i32x4*>(a.y + (size_t)img * a.y_cp + a.y_off + ch3 + 16 * half) = i32x4{(int)o[0], (int)o[1], (int)o[2], (int)o[3]};
     }
   }
-  BG_STAMP(10);
-#undef BG_STAMP
+  TF2_BLOCK_STAMP(dbg, 10);
   if (!last) bg_signal(c.b[kb + 1].ctr + (size_t)img * 32, m, tag, tid);      // stores acknowledged, LDS free, then "my output is complete"
   }
 }

@@ -12,7 +12,7 @@
 //   * a block owns R output rows x the full width W of one image (R * W <= TN pixels) and ALL C channels of the 3x3;
 //   * the 3x3's input is fetched ONCE: the (R+2) x (W+2) halo tile (zero border = the padding of sequencer.cl:287) goes
 //     global -> LDS by LDS-DMA in the prologue; the B operand of tap (dh, dw) is the same tile read at a shifted pixel
-//     address (ds_read_b128, XOR-swizzled rows: any 16 consecutive pixels hit 16 distinct bank groups);
+//     address (ds_read_b128, XOR-swizzled rows: any 16 consecutive pixels hit 16 distinct bank groups -- lds_tile.h);
 //   * weights (A operand) go global -> registers: a lane's MFMA fragment is 16 contiguous bytes of its row in the packed
 //     tile; the next step's fragments are loaded while the current MFMAs run.  Two-window layers (weight_pack.cpp "dual")
 //     are swept window by window into ONE accumulator with the Horner shift in between (the B operand sits in LDS, so
@@ -31,19 +31,9 @@
 #include "tf2_internal.h"
 #include "tf2_device.h"
 #include "requant_epilogue.h"
+#include "lds_tile.h"
 
 namespace tf2 {
-
-using i32x4 = int __attribute__((ext_vector_type(4)));
-using i32x16 = int __attribute__((ext_vector_type(16)));
-
-#define TF2_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define TF2_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
-
-template <int T, int N, class F>
-__device__ __forceinline__ void bn_static_for(F& fn) {
-  if constexpr (T < N) { fn(std::integral_constant<int, T>{}); bn_static_for<T + 1, N>(fn); }
-}
 
 constexpr int kBneckPasses = 4;
 #ifndef TF2_BNECK_PF
@@ -74,12 +64,7 @@ __global__ __launch_bounds__(512, 4) void conv_bneck_kernel(BneckArgs a) {
   int* const prm2 = reinterpret_cast<int*>(reinterpret_cast<int8_t*>(prm1) + a.hdr1_used);
 
   // XCD-aware remap: consecutive tiles (neighbouring row bands of one image share halo rows) on one XCD
-  const int nblk = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, within = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
-  }
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int img = bid / a.tiles_per_img;
   const int r0 = (bid - img * a.tiles_per_img) * R;
   const int rows = (a.H - r0) < R ? (a.H - r0) : R;      // valid output rows of this tile
@@ -93,31 +78,29 @@ __global__ __launch_bounds__(512, 4) void conv_bneck_kernel(BneckArgs a) {
   {
     const int8_t* h1 = reinterpret_cast<const int8_t*>(a.hdr1) + lane * 16;
     for (int i = wave; i * 1024 < a.hdr1_used; i += 8)
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(h1 + i * 1024), TF2_LDS_PTR(reinterpret_cast<int8_t*>(prm1) + i * 1024), 16, 0, 0);
+      lds_dma16(h1 + i * 1024, reinterpret_cast<int8_t*>(prm1) + i * 1024);
     const int per = a.hdr2_used >> 10;
     for (int i = wave; i < kBneckPasses * per; i += 8) {
       const int mt = i / per, k = i - mt * per;
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(reinterpret_cast<const int8_t*>(a.hdr2) + (size_t)mt * a.hdr2_bytes + k * 1024 + lane * 16),
-                                       TF2_LDS_PTR(reinterpret_cast<int8_t*>(prm2) + i * 1024), 16, 0, 0);
+      lds_dma16(reinterpret_cast<const int8_t*>(a.hdr2) + (size_t)mt * a.hdr2_bytes + k * 1024 + lane * 16, reinterpret_cast<int8_t*>(prm2) + i * 1024);
     }
-    // halo tile: lane l of a DMA instruction fills pixel row (l >> 2), 16-byte slot (l & 3) of a 16-pixel group; with the
-    // XOR swizzle slot c' of pixel h holds chunk c' ^ ((h >> 2) & 3)
-    const int chunk = (lane & 3) ^ ((lane >> 4) & 3);
+    // halo tile, [pixel][64] swizzled per slab: what this lane fetches of a 16-pixel group (lds_tile.h)
+    const int chunk = dma_lane_chunk(lane);
     const int n_grp = (n_h + 15) >> 4;
     for (int gi = wave; gi < n_grp * NSL; gi += 8) {
       const int s = gi / n_grp, grp = gi - s * n_grp;
-      const int h = grp * 16 + (lane >> 2);
+      const int h = grp * 16 + dma_lane_row(lane);
       const int hr = fast_div(h, a.wp_m, a.wp_s), hc = h - hr * Wp;
       const int row = r0 - 1 + hr, col = hc - 1;
       const bool ok = h < n_h && (unsigned)row < (unsigned)a.H && (unsigned)col < (unsigned)W;
       const int8_t* src = ok ? a.x + (((long long)img * a.H + row) * W + col) * TM + s * 64 + chunk * 16
                              : a.zero + s * 64 + chunk * 16;       // the stored form of x = 0: the zero page, or the 3x3's pad row
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(mid1 + s * slabb + grp * 1024), 16, 0, 0);
+      lds_dma16(src, mid1 + s * slabb + grp * 1024);
     }
   }
   // per-lane B addresses inside the halo tile: pixel p = (r, c) -> halo pixel h0 + dh * (W + 2) + dw for tap (dh, dw), byte
-  // address h * 64 + ((chunk ^ ((h >> 2) & 3)) << 4); the second K half (ks = 1) is the same address ^ 32 (chunk 2 + half =
-  // half ^ 2 under the swizzle).  Recomputed per step (4 VALU per address) rather than kept in 18 registers.
+  // address swz_off(h, half); the second K half (ks = 1) is the same address ^ 32 (lds_tile.h).  Recomputed per step (4 VALU per
+  // address) rather than kept in 18 registers.
   int h0[NTN];
 #pragma unroll
   for (int j = 0; j < NTN; j++) {
@@ -128,7 +111,7 @@ __global__ __launch_bounds__(512, 4) void conv_bneck_kernel(BneckArgs a) {
   }
   auto baddr = [&](int t, int j) {
     const int h = h0[j] + (t / 3) * Wp + t % 3;
-    return h * 64 + ((half ^ ((h >> 2) & 3)) << 4);
+    return swz_off(h, half);
   };
 
   struct Afr { i32x4 k[2]; };                            // the two K halves of one window of one weight tile
@@ -194,7 +177,7 @@ __global__ __launch_bounds__(512, 4) void conv_bneck_kernel(BneckArgs a) {
     }
     __builtin_amdgcn_sched_barrier(0);                   // steps stay in order: the unrolled loop must not pile up loads
   };
-  bn_static_for<0, NW1 * NE1>(step1);
+  static_for<0, NW1 * NE1>(step1);
   BN_STAMP(3);
   // ---- hand-over: requantise the 3x3 (window combine, pe.cl:185-203, ReLU) into the mid tile -------------------------------
   {
@@ -218,7 +201,7 @@ __global__ __launch_bounds__(512, 4) void conv_bneck_kernel(BneckArgs a) {
         const i32x4 out = outs[j];
         const int row = wn * WTN + j * 32 + (lane & 31);
         const int c = (chl & 63) >> 4;
-        *reinterpret_cast<i32x4*>(mid2 + (chl >> 6) * (TN * 64) + row * 64 + ((c ^ ((row >> 2) & 3)) << 4)) = out;
+        *reinterpret_cast<i32x4*>(swz_at(mid2 + (chl >> 6) * (TN * 64), row, c)) = out;
         if (a.keep_mid && row < n_px)
           *reinterpret_cast<i32x4*>(a.y_mid + (size_t)(pix_base + row) * a.ymid_cp + chl) = out;
       }
@@ -248,7 +231,7 @@ __global__ __launch_bounds__(512, 4) void conv_bneck_kernel(BneckArgs a) {
     const int rlo = a.add_relu ? 0 : -128;
     const int n_t = (n_px + 31) >> 5;                      // column tiles that hold pixels
     const int frow = lane & 31;
-    const int fr0 = frow * 64 + ((half ^ ((frow >> 2) & 3)) << 4);
+    const int fr0 = swz_off(frow, half);
     struct Afr2 { i32x4 k[NW2][NSL][2]; };
 #pragma unroll 1
     for (int gp = 0; gp < NGRP; gp++) {

@@ -30,25 +30,11 @@
 #include "tf2_internal.h"
 #include "tf2_device.h"
 #include "requant_epilogue.h"
-#include "vm_track.h"
+#include "lds_tile.h"
 
 namespace tf2 {
 
-using i32x4 = int __attribute__((ext_vector_type(4)));
-using i32x16 = int __attribute__((ext_vector_type(16)));
-
-#define TF2_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
-
-template <int T, int N, class F>
-__device__ __forceinline__ void c3_static_for(F& fn) {
-  if constexpr (T < N) { fn(std::integral_constant<int, T>{}); c3_static_for<T + 1, N>(fn); }
-}
-
-// LDS-DMA hidden from the compiler's wait-count pass (conv_bband.hip bb_dma16): every wait for these is written out below
-__device__ __forceinline__ void c3_dma16(const int8_t* src, int8_t* lds_dst) {
-  const unsigned l = (unsigned)(unsigned long long)TF2_LDS_PTR(lds_dst);
-  asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(src), "s"(l) : "memory", "m0");
-}
+// LDS-DMA hidden from the compiler's wait-count pass (vm_track.h dma16_hidden): every wait for these is written out below
 
 #ifdef TF2_CHECK_DMA
 TF2_DMA_CHECK_COUNTERS(g_c3_dma_check);
@@ -122,11 +108,7 @@ __global__ __launch_bounds__(512, (TMK == 64 && !PERSIST) ? 4 : 2) void conv_c3_
   const int tms = a.tm == 128 ? 7 : 6;
   const int hst = (DUAL ? 28 : 20) << tms;                 // bytes of one storage m-tile's header image
   // the bands of one image on one XCD (they share halo rows, and all of them the weights)
-  int bid = blockIdx.x;
-  {
-    const int nblk = gridDim.x, q = nblk >> 3, r = nblk & 7, xcd = bid & 7, within = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
-  }
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int cb = blockIdx.y * TMK + wm * (32 * MT);        // this wave's first output channel
   // A block walks pixel tiles bid, bid + gridDim.x, ... of its channel group (the host caps the grid at what the chip holds at once):
   // the chunk stream runs on across tiles -- while the last chunk of a tile is multiplied, the first chunk of the NEXT tile lands in
@@ -168,19 +150,18 @@ __global__ __launch_bounds__(512, (TMK == 64 && !PERSIST) ? 4 : 2) void conv_c3_
 #ifdef TF2_CHECK_DMA
         dma_stamp(buf + sl * kC3SlabB + k * kC3PlaneB + g * 1024);
 #endif
-        c3_dma16(src, buf + sl * kC3SlabB + k * kC3PlaneB + g * 1024);
+        dma16_hidden(src, buf + sl * kC3SlabB + k * kC3PlaneB + g * 1024);
       }
     }
   };
   long long* const dbg = a.dbg ? a.dbg + (size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 16 : nullptr;     // tools/c3_timeline.py: 100 MHz wall clock
-#define C3_STAMP(i) do { if (dbg && tid == 0) dbg[i] = (long long)wall_clock64(); } while (0)
   // fetch the producer's next chunk into `buf` (nothing once the block's last tile is complete) and advance
   auto produce = [&](int8_t* buf) __attribute__((always_inline)) {
     if (unit_p >= n_units) return;
     issue_chunk(unit_p, c_p, buf);
     if (++c_p == NC) { c_p = 0; unit_p += ustride; }
   };
-  C3_STAMP(0);
+  TF2_BLOCK_STAMP(dbg, 0);
   produce(ring);
   produce(ring + CHUNK);
   // header images of the block's channels (rows {bias | dbl, alpha, addend64} | lo | dshift[P]) by ordinary loads
@@ -238,7 +219,7 @@ __global__ __launch_bounds__(512, (TMK == 64 && !PERSIST) ? 4 : 2) void conv_c3_
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                            // chunks 0 and 1, header: complete in every wave
   asm volatile("" ::: "memory");
-  C3_STAMP(1);
+  TF2_BLOCK_STAMP(dbg, 1);
 
   // Everything from here on exists twice: for waves all of whose J column tiles hold pixels of the tile, and for waves whose LAST
   // one lies beyond it (4 x 56 and 7 x 28 pixel tiles fill 7 of 8 column tiles) -- chosen once per wave, so that the K loop is
@@ -325,10 +306,10 @@ __global__ __launch_bounds__(512, (TMK == 64 && !PERSIST) ? 4 : 2) void conv_c3_
       }
       __builtin_amdgcn_sched_barrier(0);
     };
-    c3_static_for<0, NSTEP>(step);
-    if (gc < 8) C3_STAMP(2 + gc);
+    static_for<0, NSTEP>(step);
+    if (gc < 8) TF2_BLOCK_STAMP(dbg, 2 + gc);
   }
-  if (unit == bid) C3_STAMP(10);
+  if (unit == bid) TF2_BLOCK_STAMP(dbg, 10);
 #undef C3_BUF
 #undef C3_BUFL
 
@@ -391,8 +372,7 @@ __global__ __launch_bounds__(512, (TMK == 64 && !PERSIST) ? 4 : 2) void conv_c3_
   }
   };
   if (n_j >= J) run(std::integral_constant<int, J>{}); else run(std::integral_constant<int, (J > 1 ? J - 1 : 1)>{});
-  C3_STAMP(11);
-#undef C3_STAMP
+  TF2_BLOCK_STAMP(dbg, 11);
 }
 
 // ---- one-slab layers (C = 64, one window, 64 output channels: VGG16's conv1_2, SSD300's) -------------------------------------------------
@@ -412,11 +392,7 @@ __global__ __launch_bounds__(512, 2) void conv_c3_w9_kernel(C3Args a) {
   const int half = lane >> 5;
   const int H = a.H, W = a.W, TH = a.TH, TW = a.TW, HC = TW + 2;
   const int tms = a.tm == 128 ? 7 : 6;
-  int bid = blockIdx.x;
-  {
-    const int nblk = gridDim.x, q = nblk >> 3, r = nblk & 7, xcd = bid & 7, within = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
-  }
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int cb = blockIdx.y * 64 + wm * 32;
   const int n_units = a.B * a.tiles_per_img, ustride = gridDim.x;
   struct Tile { int r0, c0, rows, cols; long long img_px; };
@@ -447,7 +423,7 @@ __global__ __launch_bounds__(512, 2) void conv_c3_w9_kernel(C3Args a) {
 #ifdef TF2_CHECK_DMA
           dma_stamp(buf + g * 1024);
 #endif
-          c3_dma16(src, buf + g * 1024);
+          dma16_hidden(src, buf + g * 1024);
         }
       }
       unit_p += ustride;

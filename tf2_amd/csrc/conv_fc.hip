@@ -19,11 +19,9 @@
 #include <cstdlib>
 #include "tf2_internal.h"
 #include "tf2_device.h"
+#include "lds_tile.h"
 
 namespace tf2 {
-
-using i32x4 = int __attribute__((ext_vector_type(4)));
-using i32x16 = int __attribute__((ext_vector_type(16)));
 
 template <bool DUAL>
 __global__ __launch_bounds__(256) void fc_partial_kernel(FcArgs a) {

@@ -20,18 +20,9 @@
 #include "tf2_internal.h"
 #include "tf2_device.h"
 #include "requant_epilogue.h"
+#include "lds_tile.h"
 
 namespace tf2 {
-
-using i32x4 = int __attribute__((ext_vector_type(4)));
-using i32x16 = int __attribute__((ext_vector_type(16)));
-
-#define TF2_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
-
-__device__ __forceinline__ void fire_dma16(const int8_t* src, int8_t* lds_dst) {
-  const unsigned l = (unsigned)(unsigned long long)TF2_LDS_PTR(lds_dst);
-  asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(src), "s"(l) : "memory", "m0");
-}
 
 // MT0: 32-row tiles of the squeeze (S <= 32: 1, else 2); DUAL1: the squeeze is a two-window layer; JW: pixel tiles per wave in the expand.
 // POOL: the module's 3x3 / stride 2 / pad 0 ceil-mode max pool (pool.cl:152-260 + pool_tail.cl:91-216; SqueezeNet 1.1's fire3 / fire5) in the
@@ -52,7 +43,7 @@ __global__ __launch_bounds__(512, 2) void conv_fire_kernel(FireArgs a) {
   const int planeb = ((n_h + 63) >> 6) * 1024;             // bytes of one 16-channel plane of the halo tile
   const int NPL = a.Sp >> 4;                               // planes
   const int tms1 = a.tm1 == 128 ? 7 : 6, tms2 = a.tm2 == 128 ? 7 : 6;
-  int8_t* const xin = lds;                                 // [KS1][NP0][64] swizzled (conv_bband.hip's chunk layout)
+  int8_t* const xin = lds;                                 // [KS1][NP0][64] swizzled (lds_tile.h)
   int8_t* const mid = xin + (size_t)KS1 * NP0 * 64;        // [NPL][planeb]
   int8_t* const hdr1 = mid + (size_t)NPL * planeb;
   const int hst1 = (DUAL1 ? 28 : 20) << tms1;              // bytes of the squeeze's (single) m-tile header: rows | lo | dshift[P]
@@ -60,11 +51,7 @@ __global__ __launch_bounds__(512, 2) void conv_fire_kernel(FireArgs a) {
   const int hst2 = 20 << tms2;
   int8_t* const cy = hdr2 + (size_t)(a.N2 >> tms2) * hst2;      // POOL: the expand tile [R * W pixels][N2 bytes], chunk-swizzled
 
-  int bid = blockIdx.x;
-  {
-    const int nblk = gridDim.x, q = nblk >> 3, r = nblk & 7, xcd = bid & 7, within = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;      // the bands of one image on one XCD (conv_bband.hip)
-  }
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);      // the bands of one image on one XCD
   const int img = bid / a.tiles_per_img;
   const int r0 = (bid - img * a.tiles_per_img) * (POOL ? 2 * a.PR : R);       // first expand row of the band
   const int rows = (H - r0) < R ? (H - r0) : R;
@@ -79,17 +66,17 @@ __global__ __launch_bounds__(512, 2) void conv_fire_kernel(FireArgs a) {
   // ---- prologue: pad fill of the halo tile, the input band, the headers ----
   for (int gi = wave; gi < NPL * (planeb >> 10); gi += 8) {
     const int k = gi / (planeb >> 10), grp = gi - k * (planeb >> 10);
-    fire_dma16(a.zero2 + k * 16, mid + k * planeb + grp * 1024);
+    dma16_hidden(a.zero2 + k * 16, mid + k * planeb + grp * 1024);
   }
   {
-    const int chunk = (lane & 3) ^ ((lane >> 4) & 3), drow = lane >> 2;
+    const int chunk = dma_lane_chunk(lane), drow = dma_lane_row(lane);
     for (int gi = wave; gi < KS1 * (NP0 / 16); gi += 8) {
       const int sl = gi / (NP0 / 16), grp = gi - sl * (NP0 / 16);
       const int p = grp * 16 + drow;
       const int row = r0 - 1 + fast_div(p, a.w_m, a.w_s);
       const bool ok = p < n_p0 && (unsigned)row < (unsigned)H;
       const int8_t* src = ok ? a.x + (size_t)(pix0 + p) * a.Cin + sl * 64 + chunk * 16 : a.zero + chunk * 16;
-      fire_dma16(src, xin + (size_t)sl * (NP0 * 64) + grp * 1024);
+      dma16_hidden(src, xin + (size_t)sl * (NP0 * 64) + grp * 1024);
     }
   }
   for (int i = tid; i < (hst1 >> 4); i += 512) reinterpret_cast<i32x4*>(hdr1)[i] = reinterpret_cast<const i32x4*>(a.hdr1)[i];
@@ -118,7 +105,7 @@ __global__ __launch_bounds__(512, 2) void conv_fire_kernel(FireArgs a) {
     const int* prm = reinterpret_cast<const int*>(hdr1);
     for (int t = wn; t < a.NT0; t += WN0) {
       const int prow = t * 32 + (lane & 31);
-      const int bm = prow * 64 + ((half ^ ((prow >> 2) & 3)) << 4);
+      const int bm = swz_off(prow, half);
       i32x16 acc, acc2;
 #pragma unroll
       for (int r = 0; r < 16; r++) { acc[r] = 0; acc2[r] = 0; }

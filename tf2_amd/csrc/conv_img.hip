@@ -10,7 +10,7 @@
 //     ragged; the last block of an odd batch holds one image);
 //   * prologue: the m-tile's header rows and the block's input -- per image the zero-padded (H + 2) x (W + 2) map, border positions
 //     filled from the row's stored zero (ConvArgs::zero: the pad row of a doubled tensor, else the zero page) -- go global -> LDS by
-//     LDS-DMA, once.  Layout: conv_bneck's halo tile (per 64-channel slab 64 bytes per pixel, the four 16-byte chunks XOR-swizzled by
+//     LDS-DMA, once.  Layout: lds_tile.h's, as conv_bneck's halo tile (per 64-channel slab 64 bytes per pixel, the four 16-byte chunks XOR-swizzled by
 //     pixel so that a tap's shifted reads spread over the banks): one DMA instruction then covers 16 pixels x 64 contiguous bytes --
 //     16 half cache lines.  (Four 16-byte planes per slab, conv_bband's mid1 layout, would make a tap an immediate offset, but a DMA
 //     instruction fills 1 KiB of ONE plane: 64 lanes on 64 different cache lines for 16 bytes each, four times the line requests of
@@ -33,19 +33,9 @@
 #include "tf2_internal.h"
 #include "tf2_device.h"
 #include "requant_epilogue.h"
+#include "lds_tile.h"
 
 namespace tf2 {
-
-using i32x4 = int __attribute__((ext_vector_type(4)));
-using i32x16 = int __attribute__((ext_vector_type(16)));
-
-#define TF2_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define TF2_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
-
-template <int T, int N, class F>
-__device__ __forceinline__ void img_static_for(F& fn) {
-  if constexpr (T < N) { fn(std::integral_constant<int, T>{}); img_static_for<T + 1, N>(fn); }
-}
 
 constexpr int kImgG = 2;                 // images per block
 constexpr int kImgWaves = 8;
@@ -96,24 +86,24 @@ __global__ __launch_bounds__(512) void conv_img_kernel(ImgArgs a) {
   {
     const int8_t* h = reinterpret_cast<const int8_t*>(a.hdr) + (size_t)mt * a.hdr_bytes + lane * 16;
     for (int i = wave; i * 1024 < a.hdr_used; i += kImgWaves)
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(h + i * 1024), TF2_LDS_PTR(reinterpret_cast<int8_t*>(prm) + i * 1024), 16, 0, 0);
-    // lane l of a DMA instruction fills pixel (l >> 2), 16-byte slot (l & 3) of a 16-pixel group; slot c' of pixel h holds chunk
-    // c' ^ ((h >> 2) & 3).  Positions of the border, of an image the batch does not have and of the group's padding take the stored zero.
-    const int chunk = (lane & 3) ^ ((lane >> 4) & 3);
+      lds_dma16(h + i * 1024, reinterpret_cast<int8_t*>(prm) + i * 1024);
+    // what this lane fetches of a 16-pixel group of the swizzled tile: lds_tile.h.  Positions of the border, of an image the batch
+    // does not have and of the group's padding take the stored zero.
+    const int chunk = dma_lane_chunk(lane);
     for (int gi = wave; gi < HGRP * NSL; gi += kImgWaves) {
       const int s = gi / HGRP, g = gi - s * HGRP;
-      const int hh = g * 16 + (lane >> 2);
+      const int hh = g * 16 + dma_lane_row(lane);
       const int hi = hh / NHALO, hq = hh - hi * NHALO;
       const int hr = hq / HP, hc = hq - hr * HP;
       const int row = hr - PAD, col = hc - PAD;
       const bool ok = hi < n_img && (unsigned)row < (unsigned)HW && (unsigned)col < (unsigned)HW;
       const int8_t* src = ok ? a.x + ((size_t)(img0 + hi) * NPIX + row * HW + col) * C + s * 64 + chunk * 16
                              : a.zero + s * 64 + chunk * 16;
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(tile + s * SLABB + g * 1024), 16, 0, 0);
+      lds_dma16(src, tile + s * SLABB + g * 1024);
     }
   }
   // per-lane B addresses: pixel p = (image, r, c) -> position h0 + dh * HP + dw of the padded maps for tap (dh, dw), byte address
-  // h * 64 + ((chunk ^ ((h >> 2) & 3)) << 4); the second K half is the same address ^ 32
+  // swz_off(h, half); the second K half is the same address ^ 32 (lds_tile.h)
   int h0[NT];
 #pragma unroll
   for (int j = 0; j < NT; j++) {
@@ -167,7 +157,7 @@ __global__ __launch_bounds__(512) void conv_img_kernel(ImgArgs a) {
 #pragma unroll
     for (int j = 0; j < NT; j++) {
       const int hh = h0[j] + toff;
-      ba[j] = hh * 64 + ((half ^ ((hh >> 2) & 3)) << 4);
+      ba[j] = swz_off(hh, half);
     }
 #pragma unroll
     for (int ks = 0; ks < 2; ks++) {
@@ -182,7 +172,7 @@ __global__ __launch_bounds__(512) void conv_img_kernel(ImgArgs a) {
     }
     __builtin_amdgcn_sched_barrier(0);                   // steps stay in order: the unrolled loop must not pile up loads
   };
-  img_static_for<0, NI>(step);
+  static_for<0, NI>(step);
 
   // ---- combining the eight partial tiles through LDS, over the input tile's space ----
   // slot s (32 KiB) holds a partial tile in the accumulators' own lane layout: 16-byte group q of tile (rt, j) at

@@ -3,8 +3,8 @@
 // Arithmetic: the reference's PE adds x * (+-2^s) into an int32 that wraps (pe.cl:27-49); here every weight row is split
 // into 7-exponent windows of int8 values that the matrix cores multiply, and the windows are recombined by left shifts --
 // the same value in Z/2^32 (proof and packed layout: weight_pack.cpp header).  Operand orientation: A = weights (rows =
-// output channels), B = gathered NHWC activations (columns = pixels); both tiles sit in LDS as 64-byte rows whose four
-// 16-byte chunks are XOR-swizzled with (row >> 2) & 3; the epilogue is requant_epilogue.h (pe.cl:185-203, relu.cl:54,
+// output channels), B = gathered NHWC activations (columns = pixels); both tiles sit in LDS as swizzled 64-byte rows
+// (lds_tile.h: the layout and the lane mapping of the DMA that fills it); the epilogue is requant_epilogue.h (pe.cl:185-203, relu.cl:54,
 // feature_writer.cl:88-122).  How operands reach the matrix cores and how little latency a block exposes:
 //
 //  * everything the K loop and the epilogue need per m-tile (bias / final shift / alpha /
@@ -20,8 +20,8 @@
 //    "Pipelining across barriers").  The K loop contains no ordinary global load and no
 //    64-bit LDS read: either makes hipcc (ROCm 7.2) drain the LDS-DMA queue with vmcnt(0)
 //    every iteration.  The LDS destination of an LDS-DMA is lane-linear, so the XOR swizzle
-//    is applied on the per-lane SOURCE address (rule 21) and again on the ds_read_b128
-//    side; zero padding (sequencer.cl:287) is a read from a zero page;
+//    is applied on the per-lane SOURCE address (lds_tile.h dma_lane_chunk) and again on the
+//    ds_read_b128 side (swz_off); zero padding (sequencer.cl:287) is a read from a zero page;
 //  * within an iteration: ds_read fragments, issue the next stage's DMAs (hides the LDS
 //    latency), then the MFMAs, which keep running while the wave moves on to the next wait;
 //  * the residual tile (feature_writer.cl:88-122) is prefetched into registers before the
@@ -35,35 +35,9 @@
 #include "tf2_internal.h"
 #include "tf2_device.h"
 #include "requant_epilogue.h"
+#include "lds_tile.h"
 
 namespace tf2 {
-
-using i32x4 = int __attribute__((ext_vector_type(4)));
-using i32x16 = int __attribute__((ext_vector_type(16)));
-
-#define TF2_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define TF2_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N <= 15, "vmcnt immediate out of the prepared range");
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else if constexpr (N == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-  else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else if constexpr (N == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-  else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-  else if constexpr (N == 11) asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
-  else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-  else if constexpr (N == 13) asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
-  else if constexpr (N == 14) asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
-}
 
 // WM x WN waves (4, 8 or 16), each wave a WTM x WTN output tile (multiples of 32), S ring stages, OCC blocks
 // per CU the register budget is set for.  A wave's instruction stream issues one instruction per ~5 ticks
@@ -121,21 +95,14 @@ __device__ __forceinline__ void conv_mfma2_body(const ConvArgs& a, const int blk
   int* const ghw = goff + a_max_ent * 4;
 
   // XCD-aware remap: consecutive logical tiles (same pixel tile, all channel tiles) on one XCD
-  const int nblk = nblk_x;
-  int bid = blk_x;
-  {
-    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, within = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
-  }
+  const int bid = xcd_remap(blk_x, nblk_x);
   const int ntile = fast_div_u(bid, mt_m, mt_s);                 // bid / n_mtiles
   const int mtile = bid - ntile * a_n_mtiles;
   const int px0 = ntile * TN;
 
-  // LDS-DMA lane l of an instruction fills row (l>>2), 16-byte slot (l&3) of a 16-row group;
-  // with the XOR swizzle slot c' of row r holds chunk c = c' ^ ((r>>2)&3), and r>>2 == l>>4
-  // inside a group, so every lane always fetches the same chunk index:
-  const int chunk = (lane & 3) ^ ((lane >> 4) & 3);
-  const int a_lane_off = (lane >> 2) * 64 + chunk * 16;       // inside a 16-row group of a weight tile
+  // what this lane fetches of every 16-row group it fills by LDS-DMA (lds_tile.h): the same chunk index whatever the group
+  const int chunk = dma_lane_chunk(lane);
+  const int a_lane_off = dma_lane_src_off(lane);       // inside a 16-row group of a weight tile
 
   // The gather words of the first S-1 stages straight from the header image in global memory with SCALAR loads
   // (constant address space, uniform address): they arrive with the kernel arguments' latency class, so the
@@ -180,7 +147,7 @@ __device__ __forceinline__ void conv_mfma2_body(const ConvArgs& a, const int blk
     const int8_t* hsrc = reinterpret_cast<const int8_t*>(ahdr) + hdr_words * 4 + lane * 16;
     int8_t* hdst = reinterpret_cast<int8_t*>(prm);
     for (int i = wave; i * 1024 < a_hdr_bytes; i += NW)
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(hsrc + i * 1024), TF2_LDS_PTR(hdst + i * 1024), 16, 0, 0);
+      lds_dma16(hsrc + i * 1024, hdst + i * 1024);
   };
   // residual tile prefetch FIRST (ordinary loads, the oldest entries of this wave's VMEM queue: every counted
   // wait below covers them; first use is in the epilogue)
@@ -210,7 +177,7 @@ __device__ __forceinline__ void conv_mfma2_body(const ConvArgs& a, const int blk
     brow_h[j] = -(1 << 20); brow_w[j] = 0; brow_ptr[j] = azero; brow_ok[j] = false;
     if (STATIC_GRP && j < NA) continue;
     if (gi >= AG && gi < NG) {
-      const int p = px0 + (gi - AG) * 16 + (lane >> 2);
+      const int p = px0 + (gi - AG) * 16 + dma_lane_row(lane);
       if (p < g.n_pix) {
         const int b = fast_div(p, g.ohw_m, g.ohw_s);
         const int rem = p - b * g.OHW;
@@ -246,7 +213,7 @@ __device__ __forceinline__ void conv_mfma2_body(const ConvArgs& a, const int blk
       const int gi = wave + NW * j;
       if (STATIC_GRP ? j < NA : gi < AG) {
         if (!((prb & kProbeNoA) && in_loop))
-        __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(wsrc + a_goff[j]), TF2_LDS_PTR(slot + gi * 1024), 16, 0, 0);
+        lds_dma16(wsrc + a_goff[j], slot + gi * 1024);
       } else if ((j < NI_LO || ni_hi) && !((prb & kProbeNoB) && in_loop)) {
         bool ok = off >= 0 && brow_ok[j];
         if (PADCHK && !(prb & kProbeNoPad)) {
@@ -254,7 +221,7 @@ __device__ __forceinline__ void conv_mfma2_body(const ConvArgs& a, const int blk
           ok = ok && (unsigned)ih < (unsigned)g.H && (unsigned)iw < (unsigned)g.W;
         }
         const int8_t* src = ok ? brow_ptr[j] + off : azero + pc;      // out of range: the stored form of x = 0 (weight_pack.cpp off_pad)
-        __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(slot + gi * 1024), 16, 0, 0);
+        lds_dma16(src, slot + gi * 1024);
       }
     }
   };
@@ -294,10 +261,10 @@ __device__ __forceinline__ void conv_mfma2_body(const ConvArgs& a, const int blk
   // ---- pipelined K loop ---------------------------------------------------------------------
   const int n_main = n_ent - (S - 1);      // iterations that still issue a stage S-1 ahead
   auto wait_main = [&]() {                 // stage `it` (and everything older) landed; S-2 younger stages may fly
-    if (ni_hi) wait_vmcnt<(S - 2) * NI_HI>(); else wait_vmcnt<(S - 2) * NI_LO>();
+    if (ni_hi) vm_wait<(S - 2) * NI_HI>(); else vm_wait<(S - 2) * NI_LO>();
   };
   // header + stage 0
-  if (n_main > 0) wait_main(); else wait_vmcnt<0>();
+  if (n_main > 0) wait_main(); else vm_wait<0>();
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   TF2_STAMP(3);
@@ -336,14 +303,14 @@ __device__ __forceinline__ void conv_mfma2_body(const ConvArgs& a, const int blk
 #pragma unroll
         for (int i = 0; i < NTM; i++) {
           const int row = wm * WTM + i * 32 + (lane & 31);
-          const int o = row * 64 + ((c ^ ((row >> 2) & 3)) << 4);
+          const int o = swz_off(row, c);
           af[i] = *reinterpret_cast<const i32x4*>(A + o);
           af2[i] = *reinterpret_cast<const i32x4*>(A + TM * 64 + o);
         }
 #pragma unroll
         for (int j = 0; j < NTN; j++) {
           const int row = wn * WTN + j * 32 + (lane & 31);
-          bf[j] = *reinterpret_cast<const i32x4*>(B + row * 64 + ((c ^ ((row >> 2) & 3)) << 4));
+          bf[j] = *reinterpret_cast<const i32x4*>(swz_at(B, row, c));
         }
         if (ks == 0) issue_next();
 #pragma unroll
@@ -363,12 +330,12 @@ __device__ __forceinline__ void conv_mfma2_body(const ConvArgs& a, const int blk
 #pragma unroll
         for (int i = 0; i < NTM; i++) {
           const int row = wm * WTM + i * 32 + (lane & 31);
-          af[ks][i] = *reinterpret_cast<const i32x4*>(A + row * 64 + ((c ^ ((row >> 2) & 3)) << 4));
+          af[ks][i] = *reinterpret_cast<const i32x4*>(swz_at(A, row, c));
         }
 #pragma unroll
         for (int j = 0; j < NTN; j++) {
           const int row = wn * WTN + j * 32 + (lane & 31);
-          bf[ks][j] = *reinterpret_cast<const i32x4*>(B + row * 64 + ((c ^ ((row >> 2) & 3)) << 4));
+          bf[ks][j] = *reinterpret_cast<const i32x4*>(swz_at(B, row, c));
         }
       }
       issue_next();
@@ -404,7 +371,7 @@ __device__ __forceinline__ void conv_mfma2_body(const ConvArgs& a, const int blk
   if (dbg_on) { adbg[8] = t_wait; adbg[9] = t_bar; adbg[10] = t_body; adbg[11] = n_main; }
   for (; it < n_ent; it++) {               // tail: nothing left to issue, wait for everything
     if (it) {
-      wait_vmcnt<0>();
+      vm_wait<0>();
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
     }

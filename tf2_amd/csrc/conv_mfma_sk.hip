@@ -20,23 +20,9 @@
 #include "tf2_internal.h"
 #include "tf2_device.h"
 #include "requant_epilogue.h"
+#include "lds_tile.h"
 
 namespace tf2 {
-
-using i32x4 = int __attribute__((ext_vector_type(4)));
-using i32x16 = int __attribute__((ext_vector_type(16)));
-
-#define TF2_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define TF2_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
-
-template <int N>
-__device__ __forceinline__ void sk_wait_vmcnt() {
-  static_assert(N == 0 || N == 1 || N == 4 || N == 8, "vmcnt immediate");
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-}
 
 // NWV = 4 or 8 waves split the slab list; with 8 the grid of a 7x7 / 14x14 layer at batch 32 (56..392 blocks) puts
 // twice as many waves on the chip and every wave walks half as many K steps; waves 0-3 run the epilogue.
@@ -76,12 +62,7 @@ __device__ __forceinline__ void conv_mfma_sk_body(const ConvArgs& a, const int b
   int* const ghw = goff + a_max_ent * 4;
   int8_t* const ring = lds + wave * RING;
 
-  const int nblk = nblk_x;
-  int bid = blk_x;
-  {
-    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, within = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
-  }
+  int bid = xcd_remap(blk_x, nblk_x);
   // KSP: ks_parts consecutive ids (one XCD, mostly) share an output tile
   int kpart = 0, kparts = 1;
   if (KSP) { kparts = a.ks_parts; const int t = bid / kparts; kpart = bid - t * kparts; bid = t; }
@@ -110,8 +91,8 @@ __device__ __forceinline__ void conv_mfma_sk_body(const ConvArgs& a, const int b
   // list index of this wave's k-th item: entry, and for DUAL the fixed window h = wave & 1
   auto ent_of = [&](int k) { const int v = wave + NWV * k; return ent_off + (DUAL ? (v >> 1) : v); };
 
-  const int chunk = (lane & 3) ^ ((lane >> 4) & 3);             // see conv_mfma2.hip
-  const int a_lane_off = (lane >> 2) * 64 + chunk * 16;
+  const int chunk = dma_lane_chunk(lane);             // lds_tile.h: what this lane fetches of a 16-row group
+  const int a_lane_off = dma_lane_src_off(lane);
   const DenseGeom dg = {a_cslabs, a_cs_m, a_cs_s, a_k, a_kk_m, a_kk_s, a_dil, g.W, g.Cp_in};
   const int lane_c16 = chunk * 16;
   auto gather_of = [&](int sl, int& off, int& hw) {             // DENSE: this lane's gather words of slab sl (entry index == slab)
@@ -127,7 +108,7 @@ __device__ __forceinline__ void conv_mfma_sk_body(const ConvArgs& a, const int b
 #pragma unroll
     for (int j = 0; j < AI; j++)
       if (!(prb & kProbeNoA) || k < S - 1)
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(wsrc + j * 1024), TF2_LDS_PTR(slot + j * 1024), 16, 0, 0);
+      lds_dma16(wsrc + j * 1024, slot + j * 1024);
   };
 
   // header (shared by the four waves) + this wave's first weight tiles
@@ -135,7 +116,7 @@ __device__ __forceinline__ void conv_mfma_sk_body(const ConvArgs& a, const int b
     const int8_t* hsrc = reinterpret_cast<const int8_t*>(ahdr) + (size_t)mtile * a_hdr_bytes + lane * 16;
     int8_t* hdst = reinterpret_cast<int8_t*>(prm);
     for (int i = wave; i * 1024 < a_hdr_bytes; i += NWV)
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(hsrc + i * 1024), TF2_LDS_PTR(hdst + i * 1024), 16, 0, 0);
+      lds_dma16(hsrc + i * 1024, hdst + i * 1024);
   }
 #pragma unroll
   for (int s = 0; s < S - 1; s++)
@@ -146,7 +127,7 @@ __device__ __forceinline__ void conv_mfma_sk_body(const ConvArgs& a, const int b
   bool brow_ok[BI];
 #pragma unroll
   for (int j = 0; j < BI; j++) {
-    const int p = px0 + j * 16 + (lane >> 2);
+    const int p = px0 + j * 16 + dma_lane_row(lane);
     if (p < px_end) {
       const int b = fast_div(p, g.ohw_m, g.ohw_s);
       const int rem = p - b * g.OHW;
@@ -184,7 +165,7 @@ __device__ __forceinline__ void conv_mfma_sk_body(const ConvArgs& a, const int b
       for (int r = 0; r < 16; r++) acc[i][j][r] = 0;
 
   if (!DENSE) {
-    if (g.has_res && wave < 4) sk_wait_vmcnt<1>(); else sk_wait_vmcnt<0>();
+    if (g.has_res && wave < 4) vm_wait<1>(); else vm_wait<0>();
     __builtin_amdgcn_s_barrier();            // header complete (all four waves' parts): the gather tables are read from it
     asm volatile("" ::: "memory");
   }
@@ -202,7 +183,7 @@ __device__ __forceinline__ void conv_mfma_sk_body(const ConvArgs& a, const int b
         ok = ok && (unsigned)ih < (unsigned)g.H && (unsigned)iw < (unsigned)g.W;
       }
       const int8_t* src = ok ? brow_ptr[j] + off : azero + pc;      // out of range: the stored form of x = 0 (off_pad)
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(slot + j * 1024), 16, 0, 0);
+      lds_dma16(src, slot + j * 1024);
     }
   };
 
@@ -256,8 +237,8 @@ __device__ __forceinline__ void conv_mfma_sk_body(const ConvArgs& a, const int b
 #pragma unroll
       for (int i = 0; i < 2; i++) {
         const int row = i * 32 + (lane & 31);
-        af[ks][i] = *reinterpret_cast<const i32x4*>(A + row * 64 + ((c ^ ((row >> 2) & 3)) << 4));
-        bf[ks][i] = *reinterpret_cast<const i32x4*>(B + row * 64 + ((c ^ ((row >> 2) & 3)) << 4));
+        af[ks][i] = *reinterpret_cast<const i32x4*>(swz_at(A, row, c));
+        bf[ks][i] = *reinterpret_cast<const i32x4*>(swz_at(B, row, c));
       }
     }
     if (issue) {
@@ -281,13 +262,13 @@ __device__ __forceinline__ void conv_mfma_sk_body(const ConvArgs& a, const int b
 
   int k = 0;
   for (; k < n_main; k++) {
-    if (k == 0) sk_wait_vmcnt<(S - 2) * BI>();
-    else sk_wait_vmcnt<(S - 2) * NI>();
+    if (k == 0) vm_wait<(S - 2) * BI>();
+    else vm_wait<(S - 2) * NI>();
     asm volatile("" ::: "memory");
     body(k, true);
   }
   for (; k < n_mine; k++) {
-    sk_wait_vmcnt<0>();
+    vm_wait<0>();
     asm volatile("" ::: "memory");
     body(k, false);
   }
@@ -295,7 +276,7 @@ __device__ __forceinline__ void conv_mfma_sk_body(const ConvArgs& a, const int b
 
   if (prb & kProbeNoEpi) return;
   // ---- reduce the four partial tiles through LDS (the rings are dead now) ---------------------
-  sk_wait_vmcnt<0>();
+  vm_wait<0>();
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   {

@@ -22,14 +22,9 @@
 #include "tf2_internal.h"
 #include "tf2_device.h"
 #include "requant_epilogue.h"
+#include "lds_tile.h"
 
 namespace tf2 {
-
-using i32x4 = int __attribute__((ext_vector_type(4)));
-using i32x16 = int __attribute__((ext_vector_type(16)));
-
-#define TF2_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define TF2_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
 template <int TM, int NSLAB, bool DUAL>
 __global__ __launch_bounds__(512, 4) void conv_pw_kernel(ConvArgs a, int n_t32, int tiles_per_chunk) {
@@ -61,7 +56,7 @@ __global__ __launch_bounds__(512, 4) void conv_pw_kernel(ConvArgs a, int n_t32, 
   {
     const int8_t* hsrc = reinterpret_cast<const int8_t*>(ahdr) + (size_t)mtile * a_hdr_bytes + lane * 16;
     for (int i = wave; i * 1024 < a_hdr_bytes; i += 8)
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(hsrc + i * 1024), TF2_LDS_PTR(lds + i * 1024), 16, 0, 0);
+      lds_dma16(hsrc + i * 1024, lds + i * 1024);
   }
   // this wave's weights -> registers: entry s of the m-tile is slab s (launcher-checked), [window][TM rows][64 B]
   i32x4 wf[NSLAB][NWIN][2];

@@ -39,23 +39,15 @@
 #include "tf2_internal.h"
 #include "tf2_device.h"
 #include "requant_epilogue.h"
+#include "lds_tile.h"
 
 namespace tf2 {
-
-using i32x4 = int __attribute__((ext_vector_type(4)));
-using i32x16 = int __attribute__((ext_vector_type(16)));
-
-#define TF2_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
 namespace {
 constexpr int kPwkHdrSlot = 1024;                        // a wave's 32 header rows (rows | lo | dshift[2]: 7 x 32 words = 896 bytes)
 
-// LDS-DMA hidden from the compiler's wait-count pass (conv_bband.hip bb_dma16): the only wait for these is the vmcnt(0) in front of
+// LDS-DMA hidden from the compiler's wait-count pass (vm_track.h dma16_hidden): the only wait for these is the vmcnt(0) in front of
 // a tile's barrier, written out below
-__device__ __forceinline__ void pwk_dma16(const int8_t* base, unsigned off, int8_t* lds_dst) {
-  const unsigned l = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)TF2_LDS_PTR(lds_dst));
-  asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(off), "s"(base), "s"(l) : "memory", "m0");
-}
 __host__ __device__ constexpr int pwk_tile_px(int ks) { return ks <= 4 ? 128 : 64; }      // pixels of a tile (32 KB at most)
 }  // namespace
 
@@ -79,7 +71,7 @@ __device__ __forceinline__ void conv_pwk_body(const ConvArgs& a, const int n_til
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave % WM, wn = wave / WM;
   const int half = lane >> 5, frow = lane & 31;
-  const int fr0 = frow * 64 + ((half ^ ((frow >> 2) & 3)) << 4);        // a lane's fragment of pixel frow of a [32][64] tile, K half 0
+  const int fr0 = swz_off(frow, half);        // a lane's fragment of pixel frow of a [32][64] tile, K half 0
   const int part = bid / n_streams, stream = bid - part * n_streams;
   const int ch = (part * WM + wm) * 32;                  // first of the wave's 32 output channels
   const int tms = tm == 128 ? 7 : 6;
@@ -87,7 +79,7 @@ __device__ __forceinline__ void conv_pwk_body(const ConvArgs& a, const int n_til
 
   // ---- a tile's pixels -> LDS: units u = wave, wave + 4, ..: (slab, 16-pixel group); every wave issues 2 KS DMAs per tile ------------
   const bool contiguous = g.stride == 1 && g.OHW == g.H * g.W;          // output pixel index == input pixel index
-  const int chunk = (lane & 3) ^ ((lane >> 4) & 3), drow = lane >> 2;
+  const int chunk = dma_lane_chunk(tid), drow = dma_lane_row(lane);          // (tid: lds_tile.h -- the same value as for the lane)
   auto issue_tile = [&](int t, int8_t* buf) __attribute__((always_inline)) {
 #pragma unroll
     for (int q = 0; q < UPW; q++) {
@@ -111,14 +103,13 @@ __device__ __forceinline__ void conv_pwk_body(const ConvArgs& a, const int n_til
       }
       // (a group wholly past the launch: the zero page -- a different base, wave-uniform)
       if (pg >= g.n_pix) { base = a.zero; off = (unsigned)(chunk * 16); }
-      pwk_dma16(base, off, buf + s * (TP * 64) + grp * 1024);
+      dma16_hidden(base, off, buf + s * (TP * 64) + grp * 1024);
     }
   };
   int t = stream;
   if (t >= n_tiles) return;
   long long* const dbg = a.dbg2 ? a.dbg2 + (size_t)blockIdx.x * 16 : nullptr;       // tools/pwk_timeline.py: 100 MHz wall clock per phase
-#define PWK_STAMP(i) do { if (dbg && tid == 0) dbg[i] = (long long)wall_clock64(); } while (0)
-  PWK_STAMP(0);
+  TF2_BLOCK_STAMP(dbg, 0);
   issue_tile(t, pixb[0]);
 
   // the wave's weight fragments: K step v = (window, slab), 16 contiguous bytes of the lane's row per K half
@@ -162,12 +153,12 @@ __device__ __forceinline__ void conv_pwk_body(const ConvArgs& a, const int n_til
 #pragma unroll 1
     for (; t < n_tiles; t += n_streams, it++) {
       // tile t landed in every wave (and every store / load this wave issued before); nobody reads the other buffer any more
-      if (it < 3) PWK_STAMP(1 + 3 * it);
+      if (it < 3) TF2_BLOCK_STAMP(dbg, 1 + 3 * it);
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      if (it < 3) PWK_STAMP(2 + 3 * it);
+      if (it < 3) TF2_BLOCK_STAMP(dbg, 2 + 3 * it);
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      if (it < 3) PWK_STAMP(3 + 3 * it);
+      if (it < 3) TF2_BLOCK_STAMP(dbg, 3 + 3 * it);
       if (t + n_streams < n_tiles) issue_tile(t + n_streams, pixb[(it + 1) & 1]);
       const int8_t* const B0 = pixb[it & 1];
       const unsigned res_u = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(t * TP) * (unsigned)g.res_cp + (unsigned)g.res_off + (unsigned)ch));
@@ -281,12 +272,12 @@ __device__ __forceinline__ void conv_pwk_body(const ConvArgs& a, const int n_til
     int it = 0;
 #pragma unroll 1
     for (; t < n_tiles; t += n_streams, it++) {
-      if (it < 3) PWK_STAMP(1 + 3 * it);
+      if (it < 3) TF2_BLOCK_STAMP(dbg, 1 + 3 * it);
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      if (it < 3) PWK_STAMP(2 + 3 * it);
+      if (it < 3) TF2_BLOCK_STAMP(dbg, 2 + 3 * it);
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      if (it < 3) PWK_STAMP(3 + 3 * it);
+      if (it < 3) TF2_BLOCK_STAMP(dbg, 3 + 3 * it);
       if (t + n_streams < n_tiles) issue_tile(t + n_streams, pixb[(it + 1) & 1]);
       const int8_t* const B0 = pixb[it & 1];
       const unsigned y_u = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(t * TP) * (unsigned)g.y_cp + (unsigned)g.y_off + (unsigned)ch));
@@ -365,12 +356,11 @@ __device__ __forceinline__ void conv_pwk_body(const ConvArgs& a, const int n_til
   else { if (g.has_res) run(std::true_type{}, std::false_type{}); else run(std::false_type{}, std::false_type{}); }
   }
   if (dbg) {
-    PWK_STAMP(10);
+    TF2_BLOCK_STAMP(dbg, 10);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    PWK_STAMP(11);
+    TF2_BLOCK_STAMP(dbg, 11);
     if (tid == 0) dbg[12] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));
   }
-#undef PWK_STAMP
 }
 
 template <int KS, int WM, bool DUAL>

@@ -28,10 +28,9 @@
 #include <hip/hip_runtime.h>
 #include "tf2_internal.h"
 #include "tf2_device.h"
+#include "lds_tile.h"
 
 namespace tf2 {
-
-using i32x4 = int __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ int requant_i8s(int acc, int alpha, int beta, int relu) {
   long long p = (long long)acc * (long long)alpha;

@@ -35,14 +35,9 @@
 #include "tf2_internal.h"
 #include "tf2_device.h"
 #include "requant_epilogue.h"
+#include "lds_tile.h"
 
 namespace tf2 {
-
-using i32x4 = int __attribute__((ext_vector_type(4)));
-using i32x16 = int __attribute__((ext_vector_type(16)));
-
-#define TF2_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define TF2_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
 constexpr int kStemTile = 64 * 32;       // bytes of one (window, tap) weight tile: 64 rows x 32 K bytes
 
@@ -57,11 +52,6 @@ __device__ __forceinline__ unsigned stem_negmag(unsigned w) {
   const unsigned m = w & 0x80808080u, s = m >> 7;
   const unsigned mask = (m - s) | m;                           // 0xff in every negative byte
   return (~w & mask) + s;                                      // (~b) + 1 per byte; b != 0 there, so no carry out
-}
-
-template <int T, int N, class F>
-__device__ __forceinline__ void stem_static_for(F& fn) {
-  if constexpr (T < N) { fn(std::integral_constant<int, T>{}); stem_static_for<T + 1, N>(fn); }
 }
 
 template <int NWIN, bool UNIT>
@@ -85,12 +75,7 @@ __global__ __launch_bounds__(512, 4) void conv_stem_kernel(StemArgs a) {
   int8_t* const unit = reinterpret_cast<int8_t*>(flag + 4);          // UNIT: [9 taps][32] mask bytes
 
   // XCD-aware remap: the bands of one image (they share two input rows with each neighbour) on one XCD
-  const int nblk = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, within = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
-  }
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int img = bid / a.bands_per_img;
   const int r0 = (bid - img * a.bands_per_img) * R;
   const int rows = (a.OH - r0) < R ? (a.OH - r0) : R;        // valid output rows of this band
@@ -103,9 +88,9 @@ __global__ __launch_bounds__(512, 4) void conv_stem_kernel(StemArgs a) {
   {
     const int8_t* hs = reinterpret_cast<const int8_t*>(a.hdr) + lane * 16;
     for (int i = wave; i * 1024 < a.hdr_used; i += 8)
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(hs + i * 1024), TF2_LDS_PTR(reinterpret_cast<int8_t*>(prm) + i * 1024), 16, 0, 0);
+      lds_dma16(hs + i * 1024, reinterpret_cast<int8_t*>(prm) + i * 1024);
     for (int i = wave; i < NWIN * 9 * (kStemTile / 1024); i += 8)
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(a.w + i * 1024 + lane * 16), TF2_LDS_PTR(wts + i * 1024), 16, 0, 0);
+      lds_dma16(a.w + i * 1024 + lane * 16, wts + i * 1024);
     // plane k of the input tile = 16-byte chunk k of every pixel: lane l of an instruction fetches pixel 64 * g + l
     const int8_t* xb = a.x + ((long long)img * a.H + r0) * W * 32;
     const int n_grp = plane >> 10;
@@ -113,7 +98,7 @@ __global__ __launch_bounds__(512, 4) void conv_stem_kernel(StemArgs a) {
       const int k = gi >= n_grp, g = gi - k * n_grp;
       const int h = g * 64 + lane;
       const int8_t* src = h < n_valid ? xb + h * 32 + k * 16 : a.zero;
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(halo + k * plane + g * 1024), 16, 0, 0);
+      lds_dma16(src, halo + k * plane + g * 1024);
     }
     if (tid == 0) *flag = 0;
     if (UNIT && tid < 18) reinterpret_cast<i32x4*>(unit)[tid] = reinterpret_cast<const i32x4*>(a.unit)[tid];
@@ -225,7 +210,7 @@ __global__ __launch_bounds__(512, 4) void conv_stem_kernel(StemArgs a) {
         }
         __builtin_amdgcn_sched_barrier(0);                   // steps stay in order: the unrolled sweep must not pile up its reads
       };
-      stem_static_for<0, NWIN * 9>(step);
+      static_for<0, NWIN * 9>(step);
       if (UNIT) {
         // S = both K halves of the pixel (lanes l and l ^ 32); acc = (acc << dshift[1][row]) + S: the Horner step of the two-window
         // form with the low window's sum supplied directly
@@ -302,12 +287,7 @@ __global__ __launch_bounds__(512, 4) void conv_stem_pipe_kernel(StemArgs a) {
   int* const flag = prm + (a.hdr_used >> 2);
   int8_t* const unit = reinterpret_cast<int8_t*>(flag + 4);
 
-  const int nblk = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, within = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
-  }
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int img = bid / a.bands_per_img;
   const int r0 = (bid - img * a.bands_per_img) * R;
   const int rows = (a.OH - r0) < R ? (a.OH - r0) : R;
@@ -319,16 +299,16 @@ __global__ __launch_bounds__(512, 4) void conv_stem_pipe_kernel(StemArgs a) {
   {
     const int8_t* hs = reinterpret_cast<const int8_t*>(a.hdr) + lane * 16;
     for (int i = wave; i * 1024 < a.hdr_used; i += 8)
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(hs + i * 1024), TF2_LDS_PTR(reinterpret_cast<int8_t*>(prm) + i * 1024), 16, 0, 0);
+      lds_dma16(hs + i * 1024, reinterpret_cast<int8_t*>(prm) + i * 1024);
     for (int i = wave; i < 9 * (kStemTile / 1024); i += 8)
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(a.w + i * 1024 + lane * 16), TF2_LDS_PTR(wts + i * 1024), 16, 0, 0);
+      lds_dma16(a.w + i * 1024 + lane * 16, wts + i * 1024);
     const int8_t* xb = a.x + ((long long)img * a.H + r0) * W * 32;
     const int n_grp = plane >> 10;
     for (int gi = wave; gi < 2 * n_grp; gi += 8) {
       const int k = gi >= n_grp, g = gi - k * n_grp;
       const int h = g * 64 + lane;
       const int8_t* src = h < n_valid ? xb + h * 32 + k * 16 : a.zero;
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(halo + k * plane + g * 1024), 16, 0, 0);
+      lds_dma16(src, halo + k * plane + g * 1024);
     }
     if (tid == 0) *flag = 0;
     if (tid < 18) reinterpret_cast<i32x4*>(unit)[tid] = reinterpret_cast<const i32x4*>(a.unit)[tid];
@@ -519,11 +499,7 @@ __global__ __launch_bounds__(512, 4) void conv_stem_pool_kernel(StemArgs a) {
   // (image, band, channel half).  Consecutive block ids go to consecutive XCDs, each with its own L2: hand every XCD a CONTIGUOUS
   // run of (band, half) so that the two halves of a band and the bands of an image -- which read the same input rows -- meet in
   // one L2 (round 3 measured 39.5 MB fetched for a 13.3 MB input with the halves on neighbouring XCDs).
-  int bid = blockIdx.x;
-  {
-    const int nblk = gridDim.x, q = nblk >> 3, r = nblk & 7, xcd = bid & 7, within = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
-  }
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int rt = bid & 1;
   const int band_lin = bid >> 1;
   const int img = band_lin / a.bands_per_img;
@@ -540,11 +516,10 @@ __global__ __launch_bounds__(512, 4) void conv_stem_pool_kernel(StemArgs a) {
   {
     const int8_t* hs = reinterpret_cast<const int8_t*>(a.hdr) + lane * 16;
     for (int i = wave; i * 1024 < a.hdr_used; i += 8)
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(hs + i * 1024), TF2_LDS_PTR(reinterpret_cast<int8_t*>(prm) + i * 1024), 16, 0, 0);
+      lds_dma16(hs + i * 1024, reinterpret_cast<int8_t*>(prm) + i * 1024);
     // this half's weights: image [tap][K half][64 rows][16] -> LDS [tap][K half][32 rows][16], one tap per DMA instruction
     for (int t = wave; t < 9; t += 8)
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(a.w + t * kStemTile + half * (kStemTile / 2) + rt * 512 + (lane & 31) * 16),
-                                       TF2_LDS_PTR(wts + t * kHalfTile), 16, 0, 0);
+      lds_dma16(a.w + t * kStemTile + half * (kStemTile / 2) + rt * 512 + (lane & 31) * 16, wts + t * kHalfTile);
     // input rows ir0 .. : tile row i holds input row cr0 + i; for the first band tile row 0 (conv row -1's first input row) is zeros
     const int8_t* xb = a.x + ((long long)img * a.H + ir0) * W * 32;
     const int n_grp = plane >> 10;
@@ -553,7 +528,7 @@ __global__ __launch_bounds__(512, 4) void conv_stem_pool_kernel(StemArgs a) {
       const int k = gi >= n_grp, g = gi - k * n_grp;
       const int h = g * 64 + lane - skip;
       const int8_t* src = (h >= 0 && h < n_valid) ? xb + h * 32 + k * 16 : a.zero;
-      __builtin_amdgcn_global_load_lds(TF2_GLOBAL_PTR(src), TF2_LDS_PTR(halo + k * plane + g * 1024), 16, 0, 0);
+      lds_dma16(src, halo + k * plane + g * 1024);
     }
     if (tid == 0) *flag = 0;
     if (tid < 18) reinterpret_cast<i32x4*>(unit)[tid] = reinterpret_cast<const i32x4*>(a.unit)[tid];

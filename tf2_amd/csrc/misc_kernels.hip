@@ -11,11 +11,9 @@
 #include "tf2_device.h"
 #include "requant_epilogue.h"
 #include "input_quant.h"
+#include "lds_tile.h"
 
 namespace tf2 {
-
-using i32x4 = int __attribute__((ext_vector_type(4)));
-using i32x16 = int __attribute__((ext_vector_type(16)));
 
 // side job of the step's first kernel: advance the workspace's step counter (conv_bgroup.hip: the value a set group flag carries)
 // and clear every flag word of the step's group launches.  Done EVERY step: the control area sits behind the tensors, and a caller
@@ -612,7 +610,7 @@ __global__ __launch_bounds__(512, 4) void conv_first_pool_kernel(FirstArgs f) {
     if (f.fast == 1) out = requant_tile16<false, 0, true>(a16, prm, 64, wr * 32 + 4 * half, 0, -128, nores, false, false);
     else out = requant_tile16<false, 0, false>(a16, prm, 64, wr * 32 + 4 * half, 0, -128, nores, false, f.fast == 2);
     if (p_raw < n_px) {
-      *reinterpret_cast<i32x4*>(cy + (size_t)p_raw * 64 + ((g_out ^ ((p_raw >> 2) & 3)) << 4)) = out;
+      *reinterpret_cast<i32x4*>(swz_at(cy, (size_t)p_raw, g_out)) = out;
       if (f.keep && chl + 16 <= f.y_nvalid) {
         const int rsel = p_raw / OW, ow = p_raw - rsel * OW;
         if ((unsigned)(oh0 + rsel) < (unsigned)OH)
@@ -636,7 +634,7 @@ __global__ __launch_bounds__(512, 4) void conv_first_pool_kernel(FirstArgs f) {
         const int ow = pw * 2 - f.ppad + j;
         if ((unsigned)ow >= (unsigned)OW) continue;
         const int p = r * OW + ow;
-        const i32x4 v = *reinterpret_cast<const i32x4*>(cy + (size_t)p * 64 + ((g ^ ((p >> 2) & 3)) << 4));
+        const i32x4 v = *reinterpret_cast<const i32x4*>(swz_at(cy, (size_t)p, g));
 #pragma unroll
         for (int q = 0; q < 4; q++) {
           me[q] = pk_max_u16(me[q], (unsigned)v[q] & 0x00ff00ffu);

@@ -1,4 +1,5 @@
-// vm_track.h -- counted waits on LDS-DMAs that are issued as inline assembly (conv_bband.hip, conv_c3.hip), gfx950.
+// vm_track.h -- counted waits on LDS-DMAs (vm_wait<N>: every conv kernel's), and the LDS-DMA issued as inline assembly together with
+// the discipline it obliges its author to (conv_bband.hip, conv_c3.hip), gfx950.
 //
 // hipcc drains the whole VMEM queue (s_waitcnt vmcnt(0)) in front of the first LDS read behind an LDS-DMA builtin, so those kernels
 // issue their DMAs as inline assembly, which the compiler's wait-count pass does not see -- and have to write every wait for them out.
@@ -25,6 +26,21 @@ template <int N>
 __device__ __forceinline__ void vm_wait() {
   static_assert(N >= 0 && N <= 63, "vmcnt has six bits");
   asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
+}
+
+// LDS-DMA as inline assembly (lane l's 16 bytes at src land at lds_dst + 16 * l, lds_dst wave-uniform): the compiler's wait-count
+// pass does not know these loads, so it neither drains the queue (vmcnt(0)) in front of the next LDS read nor orders them against
+// anything -- every wait for them is written out by the kernel (the counter is in order: a counted wait for a younger ordinary load
+// covers every older DMA)
+__device__ __forceinline__ void dma16_hidden(const int8_t* src, int8_t* lds_dst) {
+  const unsigned l = (unsigned)(unsigned long long)(__attribute__((address_space(3))) void*)lds_dst;
+  asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(src), "s"(l) : "memory", "m0");
+}
+// ... the base + offset form: base wave-uniform (an SGPR pair), off this lane's byte offset (lds_dst is told to be uniform: behind
+// a run-time unit loop the compiler does not always see it)
+__device__ __forceinline__ void dma16_hidden(const int8_t* base, unsigned off, int8_t* lds_dst) {
+  const unsigned l = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)(__attribute__((address_space(3))) void*)lds_dst);
+  asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(off), "s"(base), "s"(l) : "memory", "m0");
 }
 
 constexpr int vm_min(int a, int b) { return a < b ? a : b; }
