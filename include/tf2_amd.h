@@ -321,6 +321,33 @@ enum {                              /* status_dev bits of a malformed record */
 tf2_status tf2_preprocess(const tf2_net* net, const tf2_preprocess_desc* d, const uint8_t* pixels_dev, size_t pixels_bytes,
                           const tf2_image_src* srcs_dev, int batch, int out_q, void* out_dev, int32_t* status_dev, void* stream);
 
+/* ---- Antialiased resize on the device (INTEGRATION.md "Antialiased resize on the device") ----
+ * tf2_preprocess with the resize of Pillow's Image.resize(size, BILINEAR) on an RGB uint8 image (ImagingResample's 8-bit path,
+ * default box, reducing_gap None) -- what torchvision's Resize does to a PIL image (data_loader.py:83-90 load_data('resnet50')) --
+ * restated bit for bit.  The same arguments, structs and records.  For one axis with n_in source and n_out resized samples, in IEEE
+ * double without contraction:
+ *   scale = n_in / n_out; fs = max(scale, 1.0); support = fs; ss = 1.0 / fs
+ *   resized index X (crop offset added): center = (X + 0.5) * scale
+ *     lo = max((int)(center - support + 0.5), 0); hi = min((int)(center + support + 0.5), n_in); n = hi - lo
+ *     w[k] = tri((((k + lo) - center) + 0.5) * ss), k = 0..n-1, tri(a) = 1 - |a| if |a| < 1 else 0
+ *     ww = w[0] + w[1] + ... in that order; if ww != 0: w[k] = w[k] / ww;  coef[k] = (int)(w[k] * 4194304.0 + 0.5)
+ * Horizontal pass first, on source rows: t[y][X][c] = clip((2097152 + sum_k src[y][lo+k][c] * coef[k]) >> 22, 0, 255) in int32, a
+ * byte; the vertical pass is the same rule on the bytes t with the row coefficients (the byte in between is part of the result).
+ * An axis whose size does not change has coefficients {2^22, 0} and returns its bytes.  Then v = (r - mean[c]) * scale[c] in
+ * float32 on the final byte r, written as float32 or quantised as tf2_preprocess does.  Only the image_h x image_w window at
+ * (crop_y, crop_x) is computed; it equals the crop of the whole resize.  round_resized is validated (0 or 1) and otherwise ignored:
+ * the resize result is bytes already.  tf2_amd.preprocess.reference_aa is the host statement (tests/golden/pil_resize.npz holds
+ * Pillow's own bytes); the device output is bit-identical to it.
+ * Host checks: those of tf2_preprocess.  Device checks: those of tf2_preprocess, and TF2_PREP_BAD_SCALE when h > 32 * resize_h or
+ * w > 32 * resize_w (an integer compare, evaluated when BAD_SIZE and BAD_RESIZE are clear): TF2_PREP_AA_MAX_SCALE bounds a filter at
+ * 65 taps an axis and with it the time of one block, and still covers short sides up to 8192 for Resize(256).  Zeros and the status
+ * bits for a malformed record, none of whose pixels is read; no read leaves the pixel buffer; no allocation, no synchronisation;
+ * enqueued on the caller's stream; the grid depends only on batch and the net's image size. */
+#define TF2_PREP_AA_MAX_SCALE 32
+enum { TF2_PREP_BAD_SCALE = 64 };   /* h > 32 * resize_h or w > 32 * resize_w (tf2_preprocess_aa only) */
+tf2_status tf2_preprocess_aa(const tf2_net* net, const tf2_preprocess_desc* d, const uint8_t* pixels_dev, size_t pixels_bytes,
+                             const tf2_image_src* srcs_dev, int batch, int out_q, void* out_dev, int32_t* status_dev, void* stream);
+
 /* ---- Second-stage crops on the device (the detect -> crop -> embed -> match cascade of faceverify/README.md; INTEGRATION.md
  * "Second-stage crops on the device") ----
  * The step between a detector's det / counts (tf2_ssd_run) and a second network's input: tf2_roi_select picks boxes into a table

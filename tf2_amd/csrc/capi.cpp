@@ -306,6 +306,12 @@ tf2_status tf2_preprocess(const tf2_net* net, const tf2_preprocess_desc* d, cons
   return preprocess(net->impl, d, pixels_dev, pixels_bytes, srcs_dev, batch, out_q, out_dev, status_dev, stream);
 }
 
+tf2_status tf2_preprocess_aa(const tf2_net* net, const tf2_preprocess_desc* d, const uint8_t* pixels_dev, size_t pixels_bytes,
+                             const tf2_image_src* srcs_dev, int batch, int out_q, void* out_dev, int32_t* status_dev, void* stream) {
+  CHECK_NET(net);
+  return preprocess_aa(net->impl, d, pixels_dev, pixels_bytes, srcs_dev, batch, out_q, out_dev, status_dev, stream);
+}
+
 tf2_status tf2_roi_select(const tf2_roi_desc* d, const float* det_dev, const int32_t* counts_dev, const tf2_image_src* srcs_dev, int batch,
                           tf2_roi* rois_dev, int32_t* roi_counts_dev, void* stream) {
   return roi_select(d, det_dev, counts_dev, srcs_dev, batch, rois_dev, roi_counts_dev, stream);

@@ -18,13 +18,26 @@ net channel c, output row y and column x of image b with source size (H, W), res
 Presets restate the per-network preprocessing of TransForm_Kit/Quantization/data_loader.py (see each one).  What they cannot
 match: cv2.resize on uint8 images (GOOGLENET's reference) is a fixed-point resize (11-bit weights) whose bytes may differ from
 this float resize + rint by one in places -- nobody has compared them; torchvision's Resize on PIL
-images (TORCHVISION) antialiases when it downscales, which this resize does not.  cv2.resize on float images (RESNET50, SSD300)
-has the same geometry, but its float32 rounding has not been compared either.
+images (TORCHVISION) antialiases when it downscales, which this resize does not -- TORCHVISION_PIL below does, bit for bit.
+cv2.resize on float images (RESNET50, SSD300) has the same geometry, but its float32 rounding has not been compared either.
+
+Antialiased resize (tf2_preprocess_aa; csrc/preprocess_aa.hip, csrc/resample_aa.h): presets with antialias=True resize as Pillow's
+Image.resize(size, BILINEAR) does on an RGB uint8 image (ImagingResample's 8-bit path, default box, reducing_gap None), which is
+integer arithmetic and is restated exactly: `resize_pil` / `reference_aa` are the statement (tests/golden/pil_resize.npz holds
+Pillow's own bytes) and the device is bit-identical to it.  For one axis with n_in source and n_out resized samples, in IEEE double:
+  scale = n_in / n_out; fs = max(scale, 1.0); support = fs; ss = 1.0 / fs
+  resized index X (crop offset added): center = (X + 0.5) * scale
+    lo = max((int)(center - support + 0.5), 0); hi = min((int)(center + support + 0.5), n_in); n = hi - lo
+    w[k] = tri((((k + lo) - center) + 0.5) * ss), tri(a) = 1 - |a| if |a| < 1 else 0;  ww = w[0] + w[1] + ... in that order
+    if ww != 0: w[k] = w[k] / ww;  coef[k] = (int)(w[k] * 4194304.0 + 0.5)
+  horizontal pass first   t[y][X][c] = clip((2097152 + sum_k src[y][lo+k][c] * coef[k]) >> 22, 0, 255) in int32, a byte
+  vertical pass           the same rule on the bytes t with the row coefficients
+  output                  v = (r - mean[c]) * scale[c] in float32 on the final byte r, as float32 or quant_input(v, 2^-Q0).
 
 `Preprocessor(net, preset)` runs the device path; `pack(images, preset, device)` builds the pixel buffer and the per-image
 records (tf2_image_src) from a list of HWC arrays, or refills buffers a captured graph reads."""
 import ctypes as C
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Optional, Tuple
 
 import numpy as np
@@ -36,7 +49,10 @@ SRC_WORDS = SRC_DTYPE.itemsize // 4
 
 # status bits of a malformed record (TF2_PREP_*, include/tf2_amd.h)
 BAD_SIZE, BAD_PITCH, BAD_OFFSET, OUT_OF_BUFFER, BAD_RESIZE, BAD_CROP = 1, 2, 4, 8, 16, 32
+BAD_SCALE = 64                  # tf2_preprocess_aa only: h > AA_MAX_SCALE * resize_h or w > AA_MAX_SCALE * resize_w
 MAX_SIDE = 32767
+AA_MAX_SCALE = 32               # TF2_PREP_AA_MAX_SCALE: a filter of at most 2 * 32 + 1 taps an axis
+AA_BITS = 22                    # fractional bits of a coefficient
 
 
 @dataclass(frozen=True)
@@ -46,7 +62,8 @@ class Preset:
       resize        fixed (RH, RW); None: out_hw (no resize for a source of that size: SqueezeNet's 227 x 227 images)
       short_side    > 0: resize the shorter side to this and the longer one to int(short_side * long / short) (torchvision Resize(int))
       center_crop   crop the out_hw window from the middle, (RH - h) / 2 rounded as torchvision's center_crop does; else `crop`
-      channels      the net's channel order over the letters of the source order ("BGR": net channel 0 is blue)"""
+      channels      the net's channel order over the letters of the source order ("BGR": net channel 0 is blue)
+      antialias     resize as Pillow's Image.resize(size, BILINEAR) does (tf2_preprocess_aa) instead of the two-tap gather"""
     name: str
     out_hw: Tuple[int, int]
     mean: Tuple[float, float, float]
@@ -57,6 +74,7 @@ class Preset:
     crop: Tuple[int, int] = (0, 0)
     center_crop: bool = False
     round_resized: bool = False
+    antialias: bool = False
 
     def geometry(self, h: int, w: int) -> Tuple[int, int, int, int]:
         """(resize_h, resize_w, crop_y, crop_x) of an h x w source"""
@@ -93,6 +111,9 @@ _TV_MEAN, _TV_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 TORCHVISION = Preset("torchvision", (224, 224), tuple(255.0 * m for m in _TV_MEAN), scale=tuple(1.0 / (255.0 * s) for s in _TV_STD),
                      channels="RGB", short_side=256, center_crop=True)
 PRESETS = {p.name: p for p in (RESNET50, GOOGLENET, SQUEEZENET, SSD300, TORCHVISION)}
+# load_data('resnet50') as torchvision runs it on PIL images: the same geometry and constants with Pillow's antialiased resize
+TORCHVISION_PIL = replace(TORCHVISION, name="torchvision_pil", antialias=True)
+AA_PRESETS = {p.name: p for p in (TORCHVISION_PIL,)}
 
 
 def src_channels(preset: Preset, src_order: str = "RGB"):
@@ -212,6 +233,92 @@ def reference(pixels, srcs, out_hw, pixel_bytes: int, src_channel, mean, scale, 
     return out, status
 
 
+def record_status_aa(srcs, pixel_bytes: int, pixels_bytes: int, out_hw) -> np.ndarray:
+    """tf2_preprocess_aa's validity rule per record: record_status, and BAD_SCALE when the source is more than AA_MAX_SCALE times
+    the resized image on an axis (an integer compare, evaluated when BAD_SIZE and BAD_RESIZE are clear)"""
+    srcs = np.asarray(srcs, SRC_DTYPE).reshape(-1)
+    out = record_status(srcs, pixel_bytes, pixels_bytes, out_hw)
+    for i, r in enumerate(srcs):
+        if not out[i] & (BAD_SIZE | BAD_RESIZE) and (int(r["h"]) > AA_MAX_SCALE * int(r["resize_h"]) or
+                                                     int(r["w"]) > AA_MAX_SCALE * int(r["resize_w"])):
+            out[i] |= BAD_SCALE
+    return out
+
+
+def aa_coefs(n_in: int, n_out: int, start: int = 0, count: Optional[int] = None):
+    """The coefficient rule of one axis (csrc/resample_aa.h: aa_axis, aa_bounds, aa_weight, aa_coef) for the resized indices
+    start .. start + count - 1: (lo int64 [count], n int64 [count], coef int32 [count, max n], zero beyond n)"""
+    count = n_out - start if count is None else count
+    scale = np.float64(n_in) / np.float64(n_out)
+    fs = max(scale, np.float64(1.0))
+    support, ss = fs, np.float64(1.0) / fs
+    center = (np.arange(start, start + count, dtype=np.float64) + 0.5) * scale
+    lo = np.maximum(np.trunc(center - support + 0.5).astype(np.int64), 0)
+    hi = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), n_in)
+    n = hi - lo
+    kmax = int(n.max()) if count else 0
+    k = np.arange(kmax, dtype=np.int64)[None, :]
+    a = np.abs((((k + lo[:, None]).astype(np.float64) - center[:, None]) + 0.5) * ss)
+    w = np.where((a < 1.0) & (k < n[:, None]), 1.0 - a, 0.0)
+    ww = np.zeros(count, np.float64)
+    for j in range(kmax):                                  # in that order: not numpy's pairwise sum (the zeros beyond n add nothing)
+        ww = ww + w[:, j]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        w = np.where(ww[:, None] != 0, w / ww[:, None], w)
+    coef = np.trunc(w * 4194304.0 + 0.5).astype(np.int32)
+    coef[k >= n[:, None]] = 0
+    return lo, n, coef
+
+
+def resample_pass(src, lo, n, coef) -> np.ndarray:
+    """One pass along axis 1 of uint8 [rows, n_in, C]: out[y, X, c] = clip((2^21 + sum_k src[y, lo[X] + k, c] * coef[X, k]) >> 22, 0, 255)
+    in int32, as bytes [rows, len(lo), C]"""
+    src = np.asarray(src, np.uint8)
+    acc = np.full((src.shape[0], len(lo), src.shape[2]), 1 << (AA_BITS - 1), np.int32)
+    for j in range(coef.shape[1]):
+        idx = np.minimum(lo + j, src.shape[1] - 1)        # (beyond n the coefficient is 0)
+        acc += src[:, idx, :].astype(np.int32) * coef[:, j][None, :, None]
+    return np.clip(acc >> AA_BITS, 0, 255).astype(np.uint8)
+
+
+def resize_pil(img, rh: int, rw: int, window=None) -> np.ndarray:
+    """Pillow's Image.resize((rw, rh), BILINEAR) of an HWC uint8 image, restated (the module docstring): uint8 [rh, rw, C], or with
+    window = (y0, x0, h_out, w_out) that window of it, uint8 [h_out, w_out, C] -- the crop of the whole resize, since every output
+    byte depends on its own row and column coefficients alone.  The horizontal pass runs first and only on the source rows the
+    vertical pass reads."""
+    img = np.asarray(img, np.uint8)
+    h, w = img.shape[:2]
+    img = img.reshape(h, w, -1)
+    y0, x0, ho, wo = window if window is not None else (0, 0, rh, rw)
+    assert 0 <= y0 and 0 <= x0 and y0 + ho <= rh and x0 + wo <= rw, "window outside the resized image"
+    xlo, xn, xcoef = aa_coefs(w, rw, x0, wo)
+    ylo, yn, ycoef = aa_coefs(h, rh, y0, ho)
+    r0, r1 = int(ylo.min()), int((ylo + yn).max())
+    t = resample_pass(img[r0:r1], xlo, xn, xcoef)                                        # [rows, wo, C]
+    return np.swapaxes(resample_pass(np.swapaxes(t, 0, 1), ylo - r0, yn, ycoef), 0, 1)   # [ho, wo, C]
+
+
+def reference_aa(pixels, srcs, out_hw, pixel_bytes: int, src_channel, mean, scale, q0: Optional[int] = None):
+    """tf2_preprocess_aa's statement on the device's own inputs, in the form of `reference`: (out, status)"""
+    pixels = np.asarray(pixels, np.uint8).reshape(-1)
+    srcs = np.asarray(srcs, SRC_DTYPE).reshape(-1)
+    oh, ow = out_hw
+    status = record_status_aa(srcs, pixel_bytes, pixels.size, out_hw)
+    out = np.zeros((len(srcs), 3, oh, ow), np.float32)
+    m32, s32 = np.asarray(mean, np.float32), np.asarray(scale, np.float32)
+    for b, r in enumerate(srcs):
+        if status[b]:
+            continue
+        res = resize_pil(source_image(pixels, r, pixel_bytes, src_channel), int(r["resize_h"]), int(r["resize_w"]),
+                         (int(r["crop_y"]), int(r["crop_x"]), oh, ow))
+        out[b] = (np.moveaxis(res, 2, 0).astype(np.float32) - m32[:, None, None]) * s32[:, None, None]
+    if q0 is not None:
+        q = quant_input(out, trans_of(q0))
+        q[status != 0] = 0
+        return q, status
+    return out, status
+
+
 def pack_host(images, preset: Preset, align: int = 1):
     """(pixels uint8 [n], srcs SRC_DTYPE [B], pixel_bytes): the images (HWC uint8, 3 or 4 bytes a pixel) back to back, each row
     starting at a multiple of `align` bytes, with resize and crop from preset.geometry"""
@@ -275,8 +382,8 @@ def reference_images(images, preset: Preset, src_order: str = "RGB", q0: Optiona
 
 
 class Preprocessor:
-    """tf2_preprocess for `net` (a tf2_amd.network.NetWork) with `preset`, on sources whose pixel bytes are the letters of
-    src_order ("RGB", "BGR", "RGBA", "BGRA"...).
+    """tf2_preprocess -- tf2_preprocess_aa when preset.antialias -- for `net` (a tf2_amd.network.NetWork) with `preset`, on
+    sources whose pixel bytes are the letters of src_order ("RGB", "BGR", "RGBA", "BGRA"...).
       pp(pixels, srcs, out="q" | "f32", stream=None) -> (images, status)
     pixels: uint8 device tensor, srcs: int32 [B, 10] device tensor of tf2_image_src records (`pack`).  images: int8 (out="q",
     quantised with the net's 2^-Q0 as tf2_net_run_q reads them) or float32 [B, 3, image_h, image_w]; status: int32 [B], 0 or the
@@ -299,8 +406,9 @@ class Preprocessor:
         with torch.cuda.stream(stream):
             res = torch.empty(B, 3, *self.out_hw, dtype=torch.int8 if out == "q" else torch.float32, device=dev)
             status = torch.empty(B, dtype=torch.int32, device=dev)
-            _lib.check(_lib.lib().tf2_preprocess(self.net._h, C.byref(self.desc), pixels.data_ptr(), pixels.numel(), srcs.data_ptr(), B,
-                                                 int(out == "q"), res.data_ptr(), status.data_ptr(), stream.cuda_stream))
+            fn = _lib.lib().tf2_preprocess_aa if self.preset.antialias else _lib.lib().tf2_preprocess
+            _lib.check(fn(self.net._h, C.byref(self.desc), pixels.data_ptr(), pixels.numel(), srcs.data_ptr(), B, int(out == "q"), res.data_ptr(),
+                          status.data_ptr(), stream.cuda_stream))
         return res, status
 
     def reference(self, pixels, srcs, out: str = "q"):
@@ -308,6 +416,9 @@ class Preprocessor:
         p = pixels.cpu().numpy() if hasattr(pixels, "cpu") else np.asarray(pixels)
         s = srcs.cpu().numpy() if hasattr(srcs, "cpu") else np.asarray(srcs)
         s = np.ascontiguousarray(s, np.int32).view(SRC_DTYPE).reshape(-1)
+        q0 = int(self.net.q[0, 0]) if out == "q" else None
+        if self.preset.antialias:
+            return reference_aa(p, s, self.out_hw, len(self.src_order), src_channels(self.preset, self.src_order),
+                                np.float32(self.preset.mean), np.float32(self.preset.scale), q0)
         return reference(p, s, self.out_hw, len(self.src_order), src_channels(self.preset, self.src_order),
-                         np.float32(self.preset.mean), np.float32(self.preset.scale), self.preset.round_resized,
-                         int(self.net.q[0, 0]) if out == "q" else None)
+                         np.float32(self.preset.mean), np.float32(self.preset.scale), self.preset.round_resized, q0)
