@@ -696,7 +696,7 @@ def test_first_bottleneck_as_one_launch_of_row_bands(r50, monkeypatch, form):
     np.testing.assert_array_equal(plain.run(x, keep_all=False), first)
 
 
-@pytest.mark.parametrize("form", ["in_flight", "alone", "single_window", "generic", "split_k_rows"])
+@pytest.mark.parametrize("form", ["in_flight", "alone", "single_window", "generic", "split_k_rows", "plain_epilogue_64_slots"])
 def test_short_k_pointwise_rows_with_the_k_extent_in_lds(r50, monkeypatch, form):
     """conv_pwk.hip (round 6): 1x1 rows of 128, 256 or 512 input channels (ResNet-50's 256 -> 64, 256 -> 128 | 512 / 2, 128 -> 512, 512 -> 256 | 1024 / 2,
     256 -> 1024, 512 -> 2048)
@@ -705,9 +705,15 @@ def test_short_k_pointwise_rows_with_the_k_extent_in_lds(r50, monkeypatch, form)
     in flight (rows of >= 4096 pixels; pwk=0: the ring kernel), pwk=2 one batch at a time as well.  Here every eligible row (pwk_minpix=0, pwk_units=0: rows of any size; pwk_slabs=8: the 512-channel rows too, which the default leaves to the ring kernel; split_k_rows: the rows the
     in-block split-K kernel would take as well), stride 1 and 2, with and without residual, one- and two-window packing, FAST and generic
     requantisation, ragged pixel counts (batch 2 / 5: tiles that straddle the end), one to eight channel parts per pixel tile, one to three tiles per block;
-    every layer against the oracle, batch-33 logits of repeated runs on the liveness-planned workspace, and against the plain launches."""
-    alone = form == "alone"
-    set_opts(monkeypatch, pwk="2" if alone else "1", pwk_minpix="0", pwk_units="0", pwk_slabs="8", alt_conc="0" if alone else "1")
+    every layer against the oracle, batch-33 logits of repeated runs on the liveness-planned workspace, and against the plain launches.
+    plain_epilogue_64_slots: the one-batch plan with pwk_pipe=0 (no requantisation between the next column group's MFMAs) and pwk_slots=64 (a quarter
+    of the blocks, four times the tiles per block) -- the two values a launch carries from the options its plan was built under -- on the ragged
+    batches only."""
+    slots64 = form == "plain_epilogue_64_slots"
+    alone = form == "alone" or slots64
+    set_opts(monkeypatch, pwk="2" if alone else "1", pwk_minpix="0", pwk_units="0", pwk_slabs=None if slots64 else "8", alt_conc="0" if alone else "1")
+    if slots64:
+        set_opts(monkeypatch, pwk_pipe="0", pwk_slots="64")
     if form == "split_k_rows":
         set_opts(monkeypatch, pwk_sk="1")
     if form == "generic":
@@ -719,6 +725,15 @@ def test_short_k_pointwise_rows_with_the_k_extent_in_lds(r50, monkeypatch, form)
     rig = Rig(t, q, model, 0)
     conc = 0 if alone else 1
     mine = {r["layer"]: r["kernel"] for r in rig.net.describe_launches(33, conc) if "conv_pwk" in r["kernel"]}
+    if slots64:
+        # a row's streams are at most 64 / channel parts, rounded up to a multiple of 8 where parts share tiles (at most 8 parts)
+        assert {5, 8, 11, 14, 27} <= set(mine) and 24 not in mine, mine
+        assert all(r["grid"] <= 64 + 7 * 8 for b in (2, 5, 33) for r in rig.net.describe_launches(b, conc) if "conv_pwk" in r["kernel"])
+        x2 = synth.synth_images(rig.t, 2, 101, kind="int8")
+        x2[0, :, :5, :] = -128
+        rig.check_all_layers(x2)
+        rig.check_all_layers(synth.synth_images(rig.t, 5, 102))
+        return
     assert {5, 8, 11, 14, 24, 27} <= set(mine) and "conv_pwk_pair_kernel" in mine[11] and "conv_pwk_pair_kernel<8 slabs" in mine[24] and 12 not in mine, mine
     if form == "split_k_rows":
         assert {30, 33} <= {r["layer"] for r in rig.net.describe_launches(2, conc) if "conv_pwk" in r["kernel"]}

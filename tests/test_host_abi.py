@@ -463,6 +463,73 @@ def test_option_string_is_parsed_once_and_checked(monkeypatch):
             assert not re.search(r"\bgetenv\s*\(\s*\"", open(os.path.join(csrc, f)).read()), f
 
 
+def test_option_table_and_its_document_name_the_same_options(monkeypatch):
+    """csrc/opt_table.h declares every option once; INTEGRATION.md section 5 names exactly those: the product options are the rows of
+    its table, the test-only ones its three lists (by when they are read).  Every test-only name is refused without TF2_AMD_TEST=1 and
+    accepted with it, and no launcher keeps option state of its own (conv_pwk's three values are RunOpts members like the rest)."""
+    csrc = os.path.join(ROOT, "tf2_amd", "csrc")
+    rows = re.findall(r"^TF2_OPT(?:_RAW)?\((\w+), (\w+), ([01]),", open(os.path.join(csrc, "opt_table.h")).read(), re.M)
+    assert len(rows) == len({n for n, _, _ in rows}) > 80
+    product = {n for n, _, test_only in rows if test_only == "0"}
+    test_only = {n for n, _, test_only in rows if test_only == "1"}
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    sec = doc[doc.index("## 5. Options"):doc.index("## 6. ")]
+    doc_product = set(re.findall(r"^\| `(\w+)=", sec, re.M))
+    lists = re.findall(r"^\* ([^:`]+)(?: \([^)]*\))?: `([^`]+)`", sec[sec.index("**Test-only options**"):], re.M)
+    doc_test_only = [n for _, names in lists for n in names.split()]
+    assert doc_product == product, doc_product ^ product
+    assert len(doc_test_only) == len(set(doc_test_only)) and set(doc_test_only) == test_only, set(doc_test_only) ^ test_only
+    assert product | test_only == {n for n, _, _ in rows} == doc_product | set(doc_test_only)
+    # ... and each list holds the options of its scope
+    scope_of = {"pack / create time": {"pack", "create"}, "launch plan": {"plan"}, "tools": {"tools"}}
+    assert [title for title, _ in lists] == list(scope_of)
+    for title, names in lists:
+        assert set(names.split()) == {n for n, scope, t in rows if t == "1" and scope in scope_of[title]}, title
+    net = network.NetWork(cfg.tiny_tables())
+    for name in sorted(test_only):
+        monkeypatch.setenv("TF2_AMD_OPTS", name + ("=0-0" if name == "skip_layers" else "=0"))
+        monkeypatch.delenv("TF2_AMD_TEST", raising=False)
+        with pytest.raises(_lib.Tf2Error, match="test-only"):
+            net.reload_options()
+        monkeypatch.setenv("TF2_AMD_TEST", "1")
+        net.reload_options()
+    monkeypatch.delenv("TF2_AMD_TEST")
+    for name in sorted(product):
+        monkeypatch.setenv("TF2_AMD_OPTS", name + "=0")
+        net.reload_options()
+    sources = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".cpp", ".h")))
+    for gone in ("conv_pwk_set_slots", "conv_pwk_set_pipe", "conv_pwk_set_min_units", "g_pwk_slots", "g_pwk_pipe", "g_pwk_min_units"):
+        assert gone not in sources, gone
+
+
+def test_a_handles_launch_plans_keep_its_own_options(golden_dir, monkeypatch):
+    """Options belong to the handle: conv_pwk's pwk_slots / pwk_units (grids and rows of the launch records) of handle A stay what A was
+    created with after handle B is created under the defaults.  (They were file-scope values of conv_pwk.hip once: B's creation reset
+    A's grids.)  The expected records are those of a single handle under the same options.  No device needed."""
+    t = cfg.resnet50_tables()
+    q = np.loadtxt(os.path.join(golden_dir, "resnet50_Q"), dtype=np.int32)
+    model = synth.synth_model(t, q, 0)
+
+    def handle():
+        net = network.NetWork(t)
+        net.Quantization(synth.q_text(q)); net.LoadModel(model); net.Pack(0)
+        return net
+
+    def pwk(net):
+        return [(r["layer"], r["kernel"], r["grid"]) for r in net.describe_launches(33, 0) if "conv_pwk" in r["kernel"]]
+    set_opts(monkeypatch, pwk="2", pwk_units="0", pwk_slots="64")
+    want = pwk(handle())
+    a = handle()
+    set_opts(monkeypatch, pwk=None, pwk_units=None, pwk_slots=None)
+    b = handle()
+    assert pwk(b) == []                                      # (one batch at a time the default plan has no conv_pwk row)
+    assert want and pwk(a) == want
+    set_opts(monkeypatch, pwk="2", pwk_units="0")            # the same rows at the default 256 slots: other grids
+    wide = pwk(handle())
+    assert [r[0] for r in wide] == [r[0] for r in want] and all(w[2] > n[2] for w, n in zip(wide, want))
+    assert pwk(a) == want
+
+
 def test_a_second_reader_of_the_image_keeps_the_plain_first_layer():
     """Net::init turns a 3x3 first layer on the 3-channel image into a pointwise layer over the im2col image -- the input TENSOR then
     holds im2col bytes.  A program in which another row reads the image as well must keep the plain form (round-4 advisor finding)."""

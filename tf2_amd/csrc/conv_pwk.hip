@@ -384,10 +384,8 @@ __global__ __launch_bounds__(256, KS * (DUAL ? 2 : 1) > 8 ? 1 : 2) void conv_pwk
 // Does the layer qualify?  1x1 / pad 0 / stride 1 or 2 (any dilation of a 1x1 is the plain layer), dense entries (every m-tile holds
 // slabs 0 .. nslab - 1 in order, one window or dual) in the layer's OWN tiles (no shared storage), K = 2 or 4 slabs, output channels a
 // multiple of the 32 x WM a block covers, no fused global average.
-static int g_pwk_min_units = 512;                        // pwk_units: fewest (tile, channel part) units of a row
-void conv_pwk_set_min_units(int u) { g_pwk_min_units = u; }
 static int pwk_wm(int Np) { return Np % 128 == 0 ? 4 : Np % 64 == 0 ? 2 : 0; }
-bool conv_pwk_eligible(const ConvArgs& a, int TM, int k, int dense, long min_pix, bool force) {
+bool conv_pwk_eligible(const ConvArgs& a, int TM, int k, int dense, long min_pix, int min_units, bool force) {
   const ConvGeom& g = a.g;
   if (k != 1 || (g.pad_h | g.pad_w) != 0 || (g.stride != 1 && g.stride != 2) || g.avg_mult) return false;
   if (!dense || (TM != 64 && TM != 128) || (a.nslab != 2 && a.nslab != 4 && a.nslab != 8) || g.Cp_in != a.nslab * 64) return false;
@@ -403,14 +401,9 @@ bool conv_pwk_eligible(const ConvArgs& a, int TM, int k, int dense, long min_pix
   // GoogLeNet's two 196-tile rows ran 1 % slower than on the ring kernel, ResNet-50's row 27 -- 49 tiles x 8 parts -- 10.3 against 8.4 us)
   const int tp = pwk_tile_px(a.nslab);
   if (force) return true;                                  // (pwk_rows: test-only)
-  if ((long)((g.n_pix + tp - 1) / tp) * (a.Np / (32 * wm)) < g_pwk_min_units) return false;
+  if ((long)((g.n_pix + tp - 1) / tp) * (a.Np / (32 * wm)) < min_units) return false;
   return g.n_pix >= min_pix;
 }
-
-static int g_pwk_slots = 256;                            // pwk_slots (test-only): blocks a launch aims at (one per CU: 3-5 tiles per block amortise a block's first-operand wait; 512 measured 0.7 % slower in flight)
-static int g_pwk_pipe = 1;                               // pwk_pipe (test-only): 0 = no requantisation between the next group's MFMAs
-void conv_pwk_set_slots(int t) { g_pwk_slots = t > 0 ? t : 256; }
-void conv_pwk_set_pipe(int p) { g_pwk_pipe = p; }
 
 // tile streams of a layer: every block walks the same number of tiles (+- 1), ~`slots` blocks in all; a multiple of 8 where channel parts share
 // tiles (block ids n_streams apart then sit on one XCD)
@@ -427,34 +420,35 @@ static int pwk_streams(const ConvArgs& a, int WM, int slots, int* n_tiles_out, i
 }
 
 template <int KS, int WM, bool DUAL>
-static int launch_pwk2(const ConvArgs& a, int TM, hipStream_t s) {
+static int launch_pwk2(const ConvArgs& a, int TM, int slots, int pipe, hipStream_t s) {
   auto fn = conv_pwk_kernel<KS, WM, DUAL>;
   int n_tiles, parts;
-  const int n_streams = pwk_streams(a, WM, g_pwk_slots, &n_tiles, &parts);
+  const int n_streams = pwk_streams(a, WM, slots, &n_tiles, &parts);
   const int grid = n_streams * parts;
   TF2_LAUNCH_NAME("conv_pwk_kernel<%d slabs,%d channel groups,%s> (%d streams of %d..%d tiles x %d channel parts)", KS, WM, DUAL ? "dual" : "single",
                   n_streams, n_tiles / n_streams, (n_tiles + n_streams - 1) / n_streams, parts);
-  TF2_LAUNCH(fn, dim3(grid), dim3(256), 0, s, a, n_tiles, TM, n_streams, g_pwk_pipe);
+  TF2_LAUNCH(fn, dim3(grid), dim3(256), 0, s, a, n_tiles, TM, n_streams, pipe);
   return launch_ok() ? 0 : -1;
 }
 
 template <int KS, int WM, bool DUAL>
-static int launch_pwk_pair2(const ConvArgs& a0, int TM0, const ConvArgs& a1, int TM1, hipStream_t s) {
+static int launch_pwk_pair2(const ConvArgs& a0, int TM0, const ConvArgs& a1, int TM1, int slots, int pipe, hipStream_t s) {
   auto fn = conv_pwk_pair_kernel<KS, WM, DUAL>;
   int nt0, p0, nt1, p1;
   // the launch aims at the same number of blocks as one row would: each row at half
-  const int ns0 = pwk_streams(a0, WM, g_pwk_slots / 2, &nt0, &p0), ns1 = pwk_streams(a1, WM, g_pwk_slots / 2, &nt1, &p1);
+  const int ns0 = pwk_streams(a0, WM, slots / 2, &nt0, &p0), ns1 = pwk_streams(a1, WM, slots / 2, &nt1, &p1);
   const int n0 = ns0 * p0, grid = n0 + ns1 * p1;
   TF2_LAUNCH_NAME("conv_pwk_pair_kernel<%d slabs,%d channel groups,%s> (%d x %d + %d x %d blocks)", KS, WM, DUAL ? "dual" : "single", ns0, p0, ns1, p1);
-  TF2_LAUNCH(fn, dim3(grid), dim3(256), 0, s, a0, a1, nt0, TM0, ns0, nt1, TM1, ns1, g_pwk_pipe, n0);
+  TF2_LAUNCH(fn, dim3(grid), dim3(256), 0, s, a0, a1, nt0, TM0, ns0, nt1, TM1, ns1, pipe, n0);
   return launch_ok() ? 0 : -1;
 }
 
-int launch_conv_pwk(const ConvArgs& a, int TM, void* stream) {
+// slots / pipe: RunOpts::pwk_slots / pwk_pipe as the launch plan recorded them (Launch::pwk_slots)
+int launch_conv_pwk(const ConvArgs& a, int TM, int slots, int pipe, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const int wm = pwk_wm(a.Np);
   const bool dual = a.dual != 0;
-#define TF2_PWK(KS_, WM_) do { return dual ? launch_pwk2<KS_, WM_, true>(a, TM, s) : launch_pwk2<KS_, WM_, false>(a, TM, s); } while (0)
+#define TF2_PWK(KS_, WM_) do { return dual ? launch_pwk2<KS_, WM_, true>(a, TM, slots, pipe, s) : launch_pwk2<KS_, WM_, false>(a, TM, slots, pipe, s); } while (0)
 #define TF2_PWK_KS(KS_) do { if (wm == 4) TF2_PWK(KS_, 4); if (wm == 2) TF2_PWK(KS_, 2); } while (0)
   if (a.nslab == 8 && wm == 4) TF2_PWK(8, 4);
   if (a.nslab == 4) TF2_PWK_KS(4);
@@ -469,12 +463,12 @@ bool conv_pwk_pair_eligible(const ConvArgs& a0, const ConvArgs& a1) {
   return a0.nslab == a1.nslab && pwk_wm(a0.Np) == pwk_wm(a1.Np) && (a0.dual != 0) == (a1.dual != 0) && !a0.dbg2 && !a1.dbg2;
 }
 
-int launch_conv_pwk_pair(const ConvArgs& a0, int TM0, const ConvArgs& a1, int TM1, void* stream) {
+int launch_conv_pwk_pair(const ConvArgs& a0, int TM0, const ConvArgs& a1, int TM1, int slots, int pipe, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (!conv_pwk_pair_eligible(a0, a1)) return 1;
   const int wm = pwk_wm(a0.Np);
   const bool dual = a0.dual != 0;
-#define TF2_PWKP(KS_, WM_) do { return dual ? launch_pwk_pair2<KS_, WM_, true>(a0, TM0, a1, TM1, s) : launch_pwk_pair2<KS_, WM_, false>(a0, TM0, a1, TM1, s); } while (0)
+#define TF2_PWKP(KS_, WM_) do { return dual ? launch_pwk_pair2<KS_, WM_, true>(a0, TM0, a1, TM1, slots, pipe, s) : launch_pwk_pair2<KS_, WM_, false>(a0, TM0, a1, TM1, slots, pipe, s); } while (0)
 #define TF2_PWKP_KS(KS_) do { if (wm == 4) TF2_PWKP(KS_, 4); if (wm == 2) TF2_PWKP(KS_, 2); } while (0)
   if (a0.nslab == 8 && wm == 4) TF2_PWKP(8, 4);
   if (a0.nslab == 4) TF2_PWKP_KS(4);

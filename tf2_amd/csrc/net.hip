@@ -44,10 +44,10 @@ tf2_status Net::init(const tf2_net_desc* d, const tf2_layer_desc* ls) {
   // per INPUT pixel for 3 channels padded to 16 -- and the layer becomes C = 27, k = 1, stride 1 on an OH x OW map: one 64-byte K slab
   // per output instead of five (nine taps of 32 bytes, 6 of them real).  Same sums term for term; the filter codes [N][3][3][3] of
   // LoadModel ARE [N][27][1][1] in that channel order, so nothing else changes (the reference does the same kind of thing for its
-  // 7x7 first layers: model_loader.cpp:244-257, input_loader.cpp:98-116).  TF2_AMD_IM2COL0=0 keeps the plain form.
+  // 7x7 first layers: model_loader.cpp:244-257, input_loader.cpp:98-116).  im2col0=0 keeps the plain form.
   im2col0 = false;
   {
-    const bool off = opt("im2col0", 1) == 0;       // (read per handle: tests build both forms)
+    const bool off = opt(OPT_im2col0) == 0;
     // (another row that reads the IMAGE would find the im2col bytes in the input tensor: such programs keep the plain form)
     bool only_consumer = true;
     for (int l = 1; l < nl; l++) if (layers[l].src == -1) only_consumer = false;
@@ -362,74 +362,21 @@ const WorkPlan* Net::plan(int batch, int mode) {
 void Net::load_options() {
   RunOpts o;
   // (the snapshot of TF2_AMD_OPTS was taken by the caller: tf2_net_create / tf2_net_reload_options, opts.h)
-  o.flags |= (int)opt("exp", 0) & 0x7ff8;    // timing-probe bits of the -DTF2_PROBES build (tf2_device.h kProbe*, tools/probe_run.py); nothing in the product reads them
-  o.pw_mode = (int)opt("pw", o.pw_mode);        // register-resident pointwise kernel: 1 auto (default), 0 never
-  o.sk_mode = (int)opt("sk", o.sk_mode);        // 0 auto, 1 force the in-block split-K kernel for every 64-row layer, 2 never
-  o.sk8_blocks = (long)opt("sk8", o.sk8_blocks);
-  o.bg_poll_limit = (long)opt("bgroup_polls", o.bg_poll_limit); o.bg_withhold = (long)opt("bgroup_withhold", 0);
-  o.sk_s3_blocks = (long)opt("sk_s3", o.sk_s3_blocks); o.sk_s3_blocks_conc = (long)opt("sk_s3_conc", o.sk_s3_blocks_conc);
-  o.fc_mode = (int)opt("fc", o.fc_mode);
-  o.fc_min_slabs = (int)opt("fc_min", o.fc_min_slabs);
-  o.c3_mode = (int)opt("c3", o.c3_mode);
-  o.c3_min_blocks = (long)opt("c3_min", o.c3_min_blocks);
-  o.img_mode = (int)opt("img", o.img_mode);             // conv_img.hip for the stride-1 rows of small maps: 0 never, 1 (default) with batches in flight, 2 always
-  o.img_min = (int)opt("img_min", o.img_min);
-  o.img_rows = (unsigned long long)opt("img_rows", 0); o.noimg_rows = (unsigned long long)opt("noimg_rows", 0);
-  o.c3_min256 = (long)opt("c3_min256", o.c3_min256);
-  o.c3_w9 = (int)opt("c3_w9", o.c3_w9);
-  o.c3_pool = (int)opt("c3_pool", o.c3_pool);
-  o.first_fuse = (int)opt("first", o.first_fuse);
-  o.first_pool = (int)opt("first_pool", o.first_pool);
-  o.fire_mode = (int)opt("fire", o.fire_mode);
-  o.fire_pool = (int)opt("fire_pool", o.fire_pool);
-  o.bneck_min_blocks = (long)opt("bneck_min", o.bneck_min_blocks);   // smallest grid that takes conv_bneck (default 200)
-  o.stem_mode = (int)opt("stem", o.stem_mode);
-  o.bgroup_min7 = (int)opt("bgroup_min7", o.bgroup_min7);    // smallest batch that takes the group launches of the 7 x 7 / 14 x 14 bottlenecks
-  o.bgroup_min14 = (int)opt("bgroup_min14", o.bgroup_min14);
-  o.bgroup_min28 = (int)opt("bgroup_min28", o.bgroup_min28);
-  o.bgroup_min56f = (int)opt("bgroup_min56f", o.bgroup_min56f);
-  o.bgroup_chain = (int)opt("bgroup_chain", o.bgroup_chain);
-  o.bgroup_mode = (int)opt("bgroup", o.bgroup_mode);     // 1: identity bottlenecks of the small maps as group launches (conv_bgroup.hip), one batch at a time
-  o.bfirst_mode = (int)opt("bfirst", o.bfirst_mode);     // the first 56 x 56 bottleneck as one launch of row bands (conv_bfirst.hip): 0 never, 1 with batches in flight, 2 always
-  o.bfirst_min = (int)opt("bfirst_min", o.bfirst_min);
-  o.bband_mode = (int)opt("bband", o.bband_mode);        // identity bottlenecks as band launches (conv_bband.hip): 0 never, 1 with batches in flight, 2 always
-  o.bband_rows = (int)opt("bband_rows", o.bband_rows);
-  o.bband_rows_alone = (int)opt("bband_rows_alone", o.bband_rows_alone);
-  o.bband_rows_dd = (int)opt("bband_rows_dd", o.bband_rows_dd);
-  o.c3_min_hw = (int)opt("c3_min_hw", o.c3_min_hw);
-  o.bband_min = (int)opt("bband_min", o.bband_min);
-  o.bband_alone_maps = (int)opt("bband_alone_maps", o.bband_alone_maps);
+#define TF2_OPT(name, scope, test_only, type, member, dflt) o.member = (type)opt(OPT_##name);
+#define TF2_OPT_RAW(name, scope, test_only, dflt)
+#include "opt_table.h"
+  // ... and the options that are more than a value copied into its member:
+  o.flags = (int)opt(OPT_exp) & 0x7ff8;          // the timing-probe bits only
+  o.dbg = (long long*)(uintptr_t)(unsigned long long)opt(OPT_dbgptr);
+  o.dbg2 = (long long*)(uintptr_t)(unsigned long long)opt(OPT_dbgptr2);
+  // alt_min moves both thresholds (a negative value counts as not given); alt_min_conc, where given, has the last word
+  if (o.alt_min_blocks < 0) o.alt_min_blocks = RunOpts().alt_min_blocks;
+  else if (opt_given(OPT_alt_min) && !opt_given(OPT_alt_min_conc)) o.alt_min_blocks_conc = o.alt_min_blocks;
   if (o.bband_mode == 2) o.bband_alone_maps = 6;
-  o.pair_mode = (int)opt("pair", o.pair_mode);          // 1 (default): independent neighbouring rows in one launch; 0: never
-  o.stem_pool = (int)opt("stem_pool", o.stem_pool);     // 1 (default): conv1's 3x3/2 max pool inside the conv_stem launch; 0: its own launch
-  o.avg_fuse = (int)opt("avg_fuse", o.avg_fuse);        // a layer's global average inside its split-K launch: 2 (default) one batch at a time, 1 always; 0: global_avg_kernel
-  o.dense_max_slabs = (int)opt("dense_max", o.dense_max_slabs);
-  o.dense_mode = (int)opt("dense", o.dense_mode);       // arithmetic gather words for dense layers: 1 (default), 0 = always the header tables
-  if (opt("alt_min", -1) >= 0) o.alt_min_blocks = o.alt_min_blocks_conc = (long)opt("alt_min", 0);       // smallest 128 x 128 grid that takes a layer's wide-tile alternative
-  o.alt_min_blocks_conc = (long)opt("alt_min_conc", o.alt_min_blocks_conc);
-  o.alt_rows = (unsigned long long)opt("alt_rows", 0); o.noalt_rows = (unsigned long long)opt("noalt_rows", 0);
-  o.sk_rows = (unsigned long long)opt("sk_rows", 0); o.nosk_rows = (unsigned long long)opt("nosk_rows", 0);
-  o.alt_narrow_blocks = (long)opt("alt_narrow", o.alt_narrow_blocks);   // a 128-row layer takes its 64-row alternative below this many 128 x 128 blocks
-  o.alt_conc_mode = (int)opt("alt_conc", o.alt_conc_mode);
-  o.pw_slabs = (int)opt("pw_slabs", o.pw_slabs);
-  o.pw_minpix = (long)opt("pw_minpix", o.pw_minpix);
-  o.pwk_mode = (int)opt("pwk", o.pwk_mode);
-  o.q128_flags = (int)opt("q128", o.q128_flags);
-  o.stem_pk_small = (int)opt("stem_pk_small", o.stem_pk_small);
-  o.sk_kb = (int)opt("sk_kb", o.sk_kb); o.sk_kb_blocks = (int)opt("sk_kb_blocks", o.sk_kb_blocks); o.sk_kb_max = (int)opt("sk_kb_max", o.sk_kb_max); o.sk_kb_min = (int)opt("sk_kb_min", o.sk_kb_min);
-  o.pwk_minpix = (long)opt("pwk_minpix", o.pwk_minpix);
-  o.pwk_sk = (int)opt("pwk_sk", o.pwk_sk);
-  o.pwk_max_slabs = (int)opt("pwk_slabs", o.pwk_max_slabs);
-  o.pwk_rows = (unsigned long long)opt("pwk_rows", 0); o.nopwk_rows = (unsigned long long)opt("nopwk_rows", 0);
-  conv_pwk_set_slots((int)opt("pwk_slots", 0));
-  conv_pwk_set_pipe((int)opt("pwk_pipe", 1));
-  conv_pwk_set_min_units((int)opt("pwk_units", 512));
-  o.dbg = (long long*)(uintptr_t)(unsigned long long)opt("dbgptr", 0);
-  o.dbg2 = (long long*)(uintptr_t)(unsigned long long)opt("dbgptr2", 0);
-  o.dbg_layer = (int)opt("dbglayer", -1);
+  if (o.pwk_slots <= 0) o.pwk_slots = 256;
   opts = o;
   launch_plans.clear();
-  // tensor lifetimes depend on which rows may share a launch (TF2_AMD_PAIR): re-plan what was planned (a caller's keep_all
+  // tensor lifetimes depend on which rows may share a launch (pair): re-plan what was planned (a caller's keep_all
   // workspace keeps being recognised by run / read_layer)
   std::vector<std::pair<int, int>> keys;
   for (const auto& kv : plans) keys.push_back(kv.first);
@@ -465,8 +412,8 @@ int Net::issue(const Launch& st, const LaunchPlan* lp, const void* images, bool 
     case Launch::CONV:
       switch (st.sel) {
         case Launch::SEL_PW: return launch_conv_pw(st.conv, st.TM, stream);
-        case Launch::SEL_PWK: return launch_conv_pwk(st.conv, st.TM, stream);
-        case Launch::SEL_PWKPAIR: return launch_conv_pwk_pair(st.conv, st.TM, st.conv2, st.TM2, stream);
+        case Launch::SEL_PWK: return launch_conv_pwk(st.conv, st.TM, st.pwk_slots, st.pwk_pipe, stream);
+        case Launch::SEL_PWKPAIR: return launch_conv_pwk_pair(st.conv, st.TM, st.conv2, st.TM2, st.pwk_slots, st.pwk_pipe, stream);
         case Launch::SEL_SK:
           if (logits && lp->logits_direct >= 0 && &st == &lp->steps[lp->logits_direct]) {
             ConvArgs cd = st.conv_direct; cd.y = logits;
@@ -627,7 +574,7 @@ tf2_status Net::run(const void* images, bool images_are_q, int batch, void* ws, 
 #ifdef TF2_PROBES
   // tools/probe_run.py: leave out the launches of a layer range (results are then wrong; only durations are read)
   int skip_lo = 1 << 30, skip_hi = -1 << 30;
-  if (const long long sk = opt("skip_layers", -1); sk >= 0) { skip_lo = (int)(sk >> 32); skip_hi = (int)(unsigned)sk; }
+  if (const long long sk = opt(OPT_skip_layers); sk >= 0) { skip_lo = (int)(sk >> 32); skip_hi = (int)(unsigned)sk; }
 #endif
   for (const Launch& st : lp->steps) {
 #ifdef TF2_PROBES

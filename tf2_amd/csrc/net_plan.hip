@@ -440,7 +440,7 @@ struct Planner {
     // short-K pointwise rows on persistent four-wave blocks (conv_pwk.hip, round 6)
     if (pwk_now(L, st) && !pl->w_share && L.concat < 0 && !(l < 64 && ((opts.nopwk_rows >> l) & 1))) {
       const bool forced = l < 64 && ((opts.pwk_rows >> l) & 1);
-      if ((forced || pl->nslab <= opts.pwk_max_slabs) && conv_pwk_eligible(ca, pl->TM, L.k, dense ? 1 : 0, opts.pwk_minpix, forced)) st.sel = Launch::SEL_PWK;
+      if ((forced || pl->nslab <= opts.pwk_max_slabs) && conv_pwk_eligible(ca, pl->TM, L.k, dense ? 1 : 0, opts.pwk_minpix, opts.pwk_min_units, forced)) { st.sel = Launch::SEL_PWK; st.pwk_slots = opts.pwk_slots; st.pwk_pipe = opts.pwk_pipe; }
     }
   }
   // a 1x1 row on the ring kernel (or, with pwk_sk, the split-K kernel) is one conv_pwk may take in this plan

@@ -55,6 +55,7 @@ struct Launch {
   int layer = -1;
   int TM = 0, signed_in = 0, mul24 = 0, shape = 0;
   int TM2 = 0;               // SEL_PWKPAIR: the second layer's tile height
+  int pwk_slots = 0, pwk_pipe = 0;   // SEL_PWK / SEL_PWKPAIR: RunOpts::pwk_slots / pwk_pipe of the options the plan was built under
   int avg_fused = 0;         // the conv launch computes the layer's global average itself (no AVG step follows)
   ConvArgs conv{};
   ConvArgs conv2{};          // SEL_PAIR: the second (independent) layer of the launch, table row layer + 1
@@ -94,64 +95,12 @@ struct LaunchPlan {
   int walkers = 0;
 };
 
-struct RunOpts {           // run-time switches, read from the TF2_AMD_OPTS snapshot (opts.h) by Net::load_options (tf2_net_reload_options)
-  int flags = 0;           // ConvGeom::flags
-  int pw_mode = 1, sk_mode = 0;
-  long bneck_min_blocks = 200;
-  int fire_mode = 2;         // fire: a fire module (squeeze + merged expands) as ONE launch (conv_fire.hip): 0 never, 1 wherever it fits, 2 (default) on maps
-                             // >= 28 wide (14 x 14 modules measured SLOWER fused: 64-128 blocks of long dependent chains, r05_experiments.txt item 10)
-  int fire_pool = 3;         // fire_pool: fire modules with a pool behind their expands: 0 never, 1 on maps >= 56 wide (the pool stays a launch), 2 wherever `fire` allows (pool a launch), 3 (default) the pool inside the fire launch where its form fits one batch at a time / as 2 with batches in flight, 4 inside always
-  int first_fuse = 1;        // first: a 3x3 / stride 1 first layer on the 3-channel image as ONE launch with its input preparation (conv_first_kernel): 1 (default) / 0
-  int first_pool = 1;        // first_pool: ... and a first layer's 3x3 / 2 max pool in that launch too (conv_first_pool_kernel): 1 (default) / 0
-  int c3_pool = 1;           // c3_pool: a layer's 2x2 / 2 max pool inside its conv_c3 launch (tiles of TH x 32 pixels): 1 (default) / 0 its own launch
-  int c3_w9 = 1;             // c3_w9: conv_c3_w9_kernel 0 never, 1 (default) where a block walks at least eight tiles, 2 wherever the layer allows it (tests)
-  int pw_slabs = 1; long pw_minpix = 8192;     // conv_pw eligibility: most K slabs, fewest pixels
-  int stem_pk_small = 1;     // stem_pk_small: conv_stem_pool_kernel at small batches with fewer pooled rows per block (a grid of >= ~192 blocks): 1 (default) / 0
-  int sk_kb = 1;             // sk_kb: split-K launches of at most sk_kb_blocks blocks (batch 1-4: the 7 x 7 and 14 x 14 maps) split K over blocks as well: 1 (default) / 0
-  int sk_kb_blocks = 8;      // sk_kb_blocks: largest grid (64 x 64 output tiles) that takes it (the 7 x 7 maps at batch 1: -3 us per 3x3 row; 16-block grids -- the 14 x 14 maps -- measured 0.3-1.4 us SLOWER: the exchange costs ~3 us)
-  int sk_kb_max = 8;         // sk_kb_max: most blocks per output tile
-  int sk_kb_min = 8;         // sk_kb_min: fewest -- the slab list must be long enough for that many parts of eight wave items (two parts of a short list cost GoogLeNet's batch-1 step 25 us)
-  int q128_flags = 1;        // q128: the input preparation tells conv_stem_pool_kernel per image whether a -128 is there (no scan of the input tile) where the step starts prep | stem + pool | conv_bfirst: 1 (default) / 0
-  int pwk_mode = 1;          // pwk: short-K pointwise rows (2 .. 8 slabs) on conv_pwk.hip (the pixel tile's whole K extent resident in LDS) instead of the ring kernel: 0 never, 1 (default) with batches in flight, 2 one batch at a time as well
-  long pwk_minpix = 4096;    // pwk_minpix: fewest output pixels
-  int pwk_max_slabs = 4;     // pwk_slabs: most K slabs of a conv_pwk row (2, 4 or 8; 8 = the 512-channel rows too: 256 registers, no overlapped epilogue -- 1.3 % slower in flight than the ring kernel's pair)
-  unsigned long long pwk_rows = 0, nopwk_rows = 0;   // test-only per-row switches (bit l = table row l): rows taken whatever pwk_units / pwk_minpix / pwk_slabs say, rows kept off
-  int pwk_sk = 0;            // pwk_sk: 1 = rows that would take the in-block split-K kernel as well
-  int c3_mode = 1;           // c3: 3x3 / 1 / pad 1 layers of big maps on conv_c3.hip (halo tile in LDS) instead of the ring kernel
-  int c3_min_hw = 14;        // c3_min_hw: smallest map side that takes conv_c3
-  long c3_min_blocks = 96;   // c3_min: smallest grid that takes it
-  int img_mode = 1;          // img: stride-1 rows of small square maps (ResNet-50's 7 x 7 x 512 3x3 rows) on conv_img.hip (whole images per block, input resident in LDS) instead of
-                             // the split-K kernel: 0 never, 1 (default) with batches in flight, 2 one batch at a time as well (the group launches keep their rows)
-  int img_min = 8;           // img_min: smallest batch that takes it (batch-1 plans keep their K-over-blocks launches)
-  unsigned long long img_rows = 0, noimg_rows = 0;   // test-only per-row switches (bit l = table row l): rows taken whatever img / img_min say, rows kept off
-  int fc_mode = 1;           // fc: whole-window layers at batch <= 32 on conv_fc.hip
-  int fc_min_slabs = 64;     // fc_min: shortest K (64-byte slabs) that takes it
-  long c3_min256 = 200;      // c3_min256: smallest grid of 256-channel blocks (one-window layers; else 128-channel blocks)
-  long alt_min_blocks = 200;   // alt_min: smallest 128 x 128 grid that takes a wide-tile alternative, one batch at a time
-  long alt_narrow_blocks = 64;     // alt_narrow
-  long alt_min_blocks_conc = 90;   // alt_min_conc: the same when the caller keeps several batches in flight
-  unsigned long long alt_rows = 0, noalt_rows = 0, sk_rows = 0, nosk_rows = 0;   // test-only per-row switches (bit l = table row l)
-  int alt_conc_mode = 2;       // alt_conc: 0 never assume concurrency, 1 always, 2 auto (calls on >= 2 streams among the last 8)
-  int dense_max_slabs = 17;   // dense_max: layers with more K slabs than this on grids of more than one round keep the header tables
-  int dense_mode = 1;      // dense: gather words of dense layers computed from the step index (1) or read from the header tables (0)
-  int bgroup_mode = 1;     // bgroup (default on): identity bottlenecks of the 14 x 14 maps in one launch, eight blocks per image (conv_bgroup.hip); one batch at a time only
-  int bgroup_chain = 5;             // consecutive identity bottlenecks of the 28 x 28 / 14 x 14 / 7 x 7 maps per group launch (1: one launch each)
-  int bgroup_min7 = 12, bgroup_min14 = 12, bgroup_min28 = 12, bgroup_min56f = 12;   // bgroup_min7 / _MIN14 / _MIN28 / _MIN56F: smallest batch that takes them (a group is 8 CUs per image whatever the batch)
-  int bfirst_mode = 2;     // bfirst: the first bottleneck of the 56 x 56 stage (shortcut | reduce, 3x3, expand) as one launch of independent row bands (conv_bfirst.hip): 0 never, 1 (default) with batches in flight, 2 one batch at a time as well (instead of the group launch)
-  int bfirst_min = 12;     // bfirst_min: smallest batch that takes it (14 blocks per image)
-  int bband_mode = 1;      // bband: identity bottlenecks as band launches (conv_bband.hip): 0 never, 1 (default) with batches in flight, 2 also one batch at a time (instead of the group launches)
-  int bband_rows_dd = 7;                      // most rows per band of a 28 x 28 bottleneck whose reduce AND 3x3 are two-window layers (rounds 4-5: 4)
-  int bband_rows = 7, bband_rows_alone = 2;   // bband_rows / _ROWS_ALONE: output rows per block (several batches in flight / one batch at a time)
-  int bband_alone_maps = 0;   // bband_alone_maps: maps that take band launches one batch at a time too, instead of the group launches (bit 1: 28 x 28, bit 2: 14 x 14; bband=2 = both)
-  int bband_min = 8;       // bband_min: smallest batch that takes them
-  int pair_mode = 1;       // pair: two independent neighbouring layers (shortcut | first 1x1) in one conv_mfma2 launch
-  int avg_fuse = 2;        // avg_fuse (0 never / 1 always / 2 one batch at a time): the global average of an end-pool layer inside its conv launch (conv_mfma_sk AVG)
-  int stem_pool = 1;       // stem_pool: fuse the first layer's 3x3 / stride 2 max pool into the conv_stem launch
-  int stem_mode = 1;       // conv_stem.hip for the executed first layer: 1 auto (default), 0 never (stem)
-  long sk_s3_blocks = 256, sk_s3_blocks_conc = 0;   // largest split-K grid on three ring stages (100 KiB of LDS: the block owns its CU), one batch at a time / in flight
-  long bg_poll_limit = 1 << 24, bg_withhold = 0;   // group launches: polls of a meeting before it is reported as failed (bgroup_polls); test-only bgroup_withhold
-  long sk8_blocks = 128;   // largest split-K grid that takes the 8-wave form (sk8)
-  long long* dbg = nullptr; long long* dbg2 = nullptr; int dbg_layer = -1;
+struct RunOpts {           // run-time switches of a handle, taken from the TF2_AMD_OPTS snapshot (opts.h) by Net::load_options (tf2_net_reload_options)
+#define TF2_OPT(name, scope, test_only, type, member, dflt) type member = dflt;      // (one member per TF2_OPT line of opt_table.h, documented there)
+#define TF2_OPT_RAW(name, scope, test_only, dflt)
+#include "opt_table.h"
+  int flags = 0;           // ConvGeom::flags (exp)
+  long long* dbg = nullptr; long long* dbg2 = nullptr;     // dbgptr, dbgptr2
 };
 
 struct Net {

@@ -115,7 +115,7 @@ tf2_status Net::pack(int mode) {
   // also pass the kernel's limits (dense weights, at most two exponent windows, LDS), else the image is repacked without it.
   std::vector<int> fuse_next(nl, 0), fused_into(nl, -1);
   std::vector<char> nofuse(nl, 0);
-  const bool fusion_on = mode == 0 && !opt_set("nofuse");
+  const bool fusion_on = mode == 0 && !opt(OPT_nofuse);
   auto decide_fusion = [&]() {
     std::fill(fuse_next.begin(), fuse_next.end(), 0); std::fill(fused_into.begin(), fused_into.end(), -1);
     if (!fusion_on) return;
@@ -150,7 +150,7 @@ tf2_status Net::pack(int mode) {
   // concat, L2Norm, final output), written by a layer with ReLU, qualify: in ResNet-50 the 64/128/256-channel tensors inside
   // the bottlenecks.  The producer's header rows carry the -128 (requant_epilogue.h).
   std::vector<std::vector<uint8_t>> dbl(nl);
-  if (mode == 0 && !opt_set("nodbl")) {
+  if (mode == 0 && !opt(OPT_nodbl)) {
     const int M = nd.max_out_channel;
     for (int p = 0; p + 1 < nl; p++) {
       const tf2_layer_desc& P_ = layers[p];
@@ -194,7 +194,7 @@ tf2_status Net::pack(int mode) {
   // ReLU and pool, adjacent slices of one concat tensor, A's channels whole 64-row tiles.  B's launch disappears: A's packed layer is
   // the 3x3 layer [A's filters as centre taps | B's filters].
   std::vector<int> merge_next(nl, 0), merged_into(nl, -1);
-  if (mode == 0 && opt("merge", 1) != 0)
+  if (mode == 0 && opt(OPT_merge) != 0)
     for (int l = 0; l + 1 < nl; l++) {
       const tf2_layer_desc& A = layers[l]; const tf2_layer_desc& B = layers[l + 1];
       if (merged_into[l] >= 0 || A.ipool || B.ipool || A.src != B.src || A.src == -1 || src_signed(A.src)) continue;
@@ -389,7 +389,7 @@ tf2_status Net::pack(int mode) {
       // slab that is non-zero in either window, holding [hi window TM x 64][lo window TM x 64].  The kernels then
       // fetch each activation slab once, keep two accumulators and combine them once at the end,
       // (hi << dshift[1]) + lo -- exact in Z/2^32 like the Horner form -- which halves the K steps.
-      const bool dual = P == 2 && !opt_set("nodual");
+      const bool dual = P == 2 && !opt(OPT_nodual);
       pl.dual = dual ? 1 : 0;
       std::vector<int32_t> dir((size_t)n_mtiles * (P + 1), 0);
       std::vector<int32_t> entries;
@@ -454,7 +454,7 @@ tf2_status Net::pack(int mode) {
         // base 0.)  Then it contributes the SAME per-pixel sum to every output channel: conv_stem adds that sum instead of sweeping
         // a second window (half the MFMAs and half the weight tile).  nounit keeps the two-window form.
         std::vector<int8_t> unit(9 * 32, 0);
-        bool unit_ok = P == 2 && !opt_set("nounit");
+        bool unit_ok = P == 2 && !opt(OPT_nounit);
         for (int t = 0; t < 9 && unit_ok; t++)
           for (int c = 0; c < 32 && unit_ok; c++) {
             const int8_t v0 = W[((size_t)1 * Np + 0) * Kp + (size_t)t * 64 + c];
@@ -488,7 +488,7 @@ tf2_status Net::pack(int mode) {
       // (Only the WIDE alternatives -- 128-row tiles as pairs of the main 64-row tiles, 22 of the 24 duplicate MB of ResNet-50 -- share
       //  by default: the narrow ones serve the tiny grids of batch 1-2, where reading halves of 8-KiB-strided tiles measured +2 % on the
       //  batch-1 latency; share=2 shares those too, share=01 none.)
-      const int share_mode = (int)opt("share", 1);
+      const int share_mode = (int)opt(OPT_share);
       if (variant == 1 && main_TM && share_mode && main_P == P && main_dual == (dual ? 1 : 0) &&
           (2 * main_TM == TM || (share_mode >= 2 && main_TM == 2 * TM))) {
         share = true;
@@ -515,10 +515,10 @@ tf2_status Net::pack(int mode) {
       // the dense window matrices: the form is used only when it reproduces them byte for byte.
       std::vector<uint8_t> nibt, lutv, clsm;
       int n_cls = 1;
-      bool fc4 = variant == 0 && mode == 0 && opt("fc4", 1) != 0 && !L.ipool && L.k == L.H && L.k == L.W && L.stride == 1 && L.dil == 1 &&
+      bool fc4 = variant == 0 && mode == 0 && opt(OPT_fc4) != 0 && !L.ipool && L.k == L.H && L.k == L.W && L.stride == 1 && L.dil == 1 &&
                  (L.pad_h | L.pad_w) == 0 && L.OH == 1 && L.OW == 1 && L.src >= 0 && L.add_src < 0 && !L.endpool && !L.pool_en && L.concat < 0 &&
                  layers[L.src].concat < 0 && l != nl - 1 && !in_signed && (P == 1 || dual) && Np % 128 == 0 && il.Cp_in % 64 == 0 &&
-                 il.Cp_in == C /* (Net::fc_at: the kernel walks whole 64-channel slabs of an unpadded tensor; C = 500 on Cp 512 stays int8 tiles for the split-K kernel) */ && Kp == Ktot && (long)entries.size() == (long)n_mtiles * nslab && nslab >= (int)opt("fc_min", 64) /* conv_fc's own threshold (RunOpts::fc_min_slabs): a layer packed this way can run nowhere else */ && fuse_next[l] <= 0 && fused_into[l] < 0;
+                 il.Cp_in == C /* (Net::fc_at: the kernel walks whole 64-channel slabs of an unpadded tensor; C = 500 on Cp 512 stays int8 tiles for the split-K kernel) */ && Kp == Ktot && (long)entries.size() == (long)n_mtiles * nslab && nslab >= (int)opt(OPT_fc_min) /* conv_fc's own threshold: a layer packed this way can run nowhere else */ && fuse_next[l] <= 0 && fused_into[l] < 0;
       if (fc4) {
         const int Mq = nd.max_out_channel;
         std::vector<int> Bc(il.Cp_in, 0), An(Np, -1000);
@@ -651,7 +651,7 @@ tf2_status Net::pack(int mode) {
       // 2^51  (x = p >> 20 fits int32 and x + 2^14 does not saturate), then
       //   y = (acc * (alpha << lo) + B') >> 35,   B' = bias * alpha + (beta << 20) + 2^34
       // is the reference result exactly, and the kernels use it (3 VALU instructions per output instead of 6).
-      bool fast = !opt_set("nofast");
+      bool fast = !opt(OPT_nofast);
       for (int n = 0; n < N && fast; n++) {
         unsigned __int128 amax = 0;
         const uint8_t* rc = m.codes.data() + (size_t)n * C * taps;
@@ -665,7 +665,7 @@ tf2_status Net::pack(int mode) {
         else if ((amax + ab) * aa + (abeta << kAlphaInflat) + (one << 34) >= (one << 51)) fast = false;
       }
       // SEMI (requant_epilogue.h): the rows that may wrap v still get the short form when x cannot leave 32 bits
-      bool semi = !fast && !opt_set("nofast") && !opt_set("nosemi");
+      bool semi = !fast && !opt(OPT_nofast) && !opt(OPT_nosemi);
       for (int n = 0; n < N && semi; n++) {
         const unsigned __int128 aa = (unsigned __int128)std::llabs((long long)m.alpha[n]);
         const unsigned __int128 abeta = (unsigned __int128)std::llabs((long long)m.beta[n]);
@@ -757,7 +757,7 @@ tf2_status Net::pack(int mode) {
       {
         const int M = nd.max_out_channel;
         std::vector<int> Bc(n_cchunk * 16, 0), An(Np, -1000);
-        bool ok4 = !opt_set("no4bit") && taps <= (in_signed ? 25 : 49);
+        bool ok4 = !opt(OPT_no4bit) && taps <= (in_signed ? 25 : 49);
         for (int pass = 0; pass < 2 && ok4; pass++) {          // pass 0: B from the input's Q row; pass 1: B = 0
           std::fill(Bc.begin(), Bc.end(), 0); std::fill(An.begin(), An.end(), -1000);
           if (pass == 0) {
