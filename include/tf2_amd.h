@@ -487,6 +487,39 @@ tf2_status tf2_emb_match(tf2_emb* m, const int8_t* out_i8_dev, int batch, const 
                          int n_rows, float threshold, void* scratch_dev, size_t scratch_bytes, int32_t* idx_dev, float* dist_dev,
                          int32_t* ids_out_dev, float* emb_out_dev, const int32_t* truth_dev, uint64_t* tally_dev, void* hip_stream);
 
+/* ---- Threshold calibration on the device (the verification curve of an embedding network; INTEGRATION.md "Threshold calibration
+ * on the device") ----
+ * Where tf2_emb_match's `threshold` comes from: the genuine and impostor distance histograms of a labelled set of float32 rows
+ * (what tf2_emb_embed writes into a gallery), from which TAR at a target FAR, the EER and the LFW fold accuracies are read.  The two
+ * calls need no handle.  tf2_amd.embed.roc_thresholds / reference_roc_hist / reference_pairs are the host statement; every count and
+ * every distance is bit-identical to them.
+ *   grid       thr[t] = (float)(t + 1) * step, t = 0 .. n_thr - 1: one float32 multiply (FaceNet's arange(0, 4, 0.01) on squared
+ *              distances is n_thr = 400, step = 0.01f).  The kernels compute it from (n_thr, step).
+ *   distance   tf2_emb_match's d for the same two rows, bit for bit: the sum over c ascending from +0 of separately rounded
+ *              (a[c] - b[c])^2; a NaN distance counts as +inf.
+ *   bin        bin(d) = #{t : thr[t] <= d} in 0..n_thr.  A pair is accepted at threshold t iff d < thr[t] iff bin(d) <= t: the
+ *              strict float32 '<' of the tally, so a threshold read off the histogram means the same thing to tf2_emb_match.
+ *   hist       int64 [2][n_thr + 1], ACCUMULATED (the caller zeroes it): hist[same][bin], same = (ids_a[i] == ids_b[j]).  Self mode
+ *              (rows_b_dev == NULL; ids_b_dev and n_b are ignored) counts every pair i < j of one set, cross mode every (i, j).  A row
+ *              whose id is < 0 takes part in no pair.  Integer adds only: exact, independent of grid, tile and order.
+ *   pairs      pairs_dev int32 [n_pairs][4] = (a, b, same, fold); dist_dev[p] = d(rows[a], rows[b]) (NaN reported as +inf), and 1 is
+ *              added to hist[fold][same][bin(d)], int64 [n_folds][2][n_thr + 1], ACCUMULATED.  A pair with a or b outside
+ *              0..n_rows-1, same not in {0, 1} or fold outside 0..n_folds-1 is invalid: it reads no row, gets dist -1.0f, adds 1 to
+ *              invalid_dev[0] (ACCUMULATED) and nothing to hist.  The check is made on the device: the host never sees the list.
+ * The all-pairs call enqueues one kernel: a block a pair of tiles of 256 rows (self mode: the pairs ti <= tj alone), every
+ * distance binned on the fly into a block-local histogram; the distance matrix is never written.  The listed-pairs call enqueues
+ * one kernel, a wave a pair.  No allocation, no synchronisation, no scratch; grids that depend on the scalar arguments alone
+ * (graph-capturable).  Host checks, before any device call (TF2_ERR_ARG with a message unless stated): d in 2..512; n_a, n_b (cross
+ * mode), n_rows, n_pairs >= 1; n_thr in 1..4096; step finite and > 0; n_folds in 1..16; non-null rows, ids (ids_b_dev in cross
+ * mode), pairs, dist, hist and invalid pointers; more than 2^31 - 1 tile pairs (TF2_ERR_UNSUPPORTED). */
+tf2_status tf2_emb_roc_hist(const float* rows_a_dev, const int32_t* ids_a_dev, int n_a,
+                            const float* rows_b_dev, const int32_t* ids_b_dev, int n_b,   /* rows_b_dev == NULL: self mode, i < j */
+                            int d, int n_thr, float step, int64_t* hist_dev /* [2][n_thr+1], ACCUMULATED */, void* hip_stream);
+tf2_status tf2_emb_roc_pairs(const float* rows_dev, int n_rows, int d, const int32_t* pairs_dev /* [n_pairs][4] */, int n_pairs,
+                             int n_folds, int n_thr, float step, float* dist_dev /* [n_pairs] */,
+                             int64_t* hist_dev /* [n_folds][2][n_thr+1], ACCUMULATED */, int64_t* invalid_dev /* [1], ACCUMULATED */,
+                             void* hip_stream);
+
 /* ---- Detection accuracy on the device (the PASCAL VOC devkit protocol behind the README's SSD mAP; INTEGRATION.md "Detection accuracy
  * on the device") ----
  * The reference ships no evaluation code (ssd.py: no weights, no dataset, no eval script), so this statement is the canonical one.

@@ -214,6 +214,8 @@ def lib() -> C.CDLL:
     L.tf2_emb_scratch_size.restype = sz
     L.tf2_emb_embed.argtypes = [vp, vp, C.c_int, vp, vp]
     L.tf2_emb_match.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, C.c_float, vp, sz, vp, vp, vp, vp, vp, vp, vp]
+    L.tf2_emb_roc_hist.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]
+    L.tf2_emb_roc_pairs.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp]
     L.tf2_det_eval_create.argtypes = [C.POINTER(DetEvalDesc), C.POINTER(vp)]
     L.tf2_det_eval_destroy.argtypes = [vp]
     L.tf2_det_eval_destroy.restype = None
@@ -236,7 +238,8 @@ EXPORTED = [
     "tf2_preprocess", "tf2_preprocess_aa", "tf2_roi_select", "tf2_roi_crop", "tf2_cls_create", "tf2_cls_destroy", "tf2_cls_run",
     "tf2_det_eval_create", "tf2_det_eval_destroy", "tf2_det_eval_store_size", "tf2_det_eval_store_init", "tf2_det_eval_run",
     "tf2_det_eval_summarise",
-    "tf2_emb_create", "tf2_emb_destroy", "tf2_emb_scratch_size", "tf2_emb_embed", "tf2_emb_match"]
+    "tf2_emb_create", "tf2_emb_destroy", "tf2_emb_scratch_size", "tf2_emb_embed", "tf2_emb_match",
+    "tf2_emb_roc_hist", "tf2_emb_roc_pairs"]
 
 
 def parse_opts(text: str) -> dict:

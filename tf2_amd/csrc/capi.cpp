@@ -9,6 +9,7 @@
 #include "classify.h"
 #include "ssd_eval.h"
 #include "embed_match.h"
+#include "embed_roc.h"
 #include "roi_crop.h"
 
 using namespace tf2;
@@ -379,6 +380,16 @@ tf2_status tf2_emb_match(tf2_emb* m, const int8_t* out_i8_dev, int batch, const 
   if (!m) { set_error("null tf2_emb handle"); return TF2_ERR_ARG; }
   return m->impl.match(out_i8_dev, batch, gallery_dev, gallery_ids_dev, n_rows, threshold, scratch_dev, scratch_bytes, idx_dev, dist_dev,
                        ids_out_dev, emb_out_dev, truth_dev, tally_dev, stream);
+}
+
+tf2_status tf2_emb_roc_hist(const float* rows_a_dev, const int32_t* ids_a_dev, int n_a, const float* rows_b_dev, const int32_t* ids_b_dev,
+                            int n_b, int d, int n_thr, float step, int64_t* hist_dev, void* stream) {
+  return emb_roc_hist(rows_a_dev, ids_a_dev, n_a, rows_b_dev, ids_b_dev, n_b, d, n_thr, step, hist_dev, stream);
+}
+
+tf2_status tf2_emb_roc_pairs(const float* rows_dev, int n_rows, int d, const int32_t* pairs_dev, int n_pairs, int n_folds, int n_thr,
+                             float step, float* dist_dev, int64_t* hist_dev, int64_t* invalid_dev, void* stream) {
+  return emb_roc_pairs(rows_dev, n_rows, d, pairs_dev, n_pairs, n_folds, n_thr, step, dist_dev, hist_dev, invalid_dev, stream);
 }
 
 tf2_status tf2_det_eval_create(const tf2_det_eval_desc* d, tf2_det_eval** out) {
