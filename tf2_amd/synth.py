@@ -169,7 +169,7 @@ def bench_network(name: str):
 
 
 # ---- extreme-regime models: parameters chosen so that the edges of the integer arithmetic are reached ----------------------------------
-EXTREME_REGIMES = ("wrap", "saturate", "spread", "shift22", "shift23", "expand32")
+EXTREME_REGIMES = ("wrap", "saturate", "spread", "shift22", "shift23", "expand32", "wrap2")
 
 
 def _stream_offsets(plan):
@@ -224,6 +224,11 @@ def synth_extreme(tables: cfg.NetTables, seed: int, regime: str, rows=None, q_sp
               22 / 23 (conv_shift.hip's mad_i32_i24 / 32-bit multiply boundary).
     expand32  the producer of a targeted row writes its channel 0 with Q -3 and the row's Q_out is 14: expand = 32 on that channel, so
               a magnitude-1 weight encodes as 0x20, which shifts by 0 (pe.cl's & 0x1f); the other channels' shifts reach 24 .. 27.
+    wrap2     wrap's Q values and BN scales (even rows SEMI, odd rows generic, chains alternate), but every weight's level is drawn
+              with probability 1/2 from 0 .. 3 and else from 13 .. 14: two exponent windows 11 .. 14 apart on every row, so that a boosted
+              row packs in the two-window ("dual") form, and with nodual=1 in the Horner form.  Every fourth output channel is
+              all-positive and every eighth (offset 2) all-negative: the inputs are post-ReLU, so those rows' high-window sums are
+              large, and both the final accumulator and hi << dshift alone leave int32 on a large share of the outputs.
     """
     assert regime in EXTREME_REGIMES, regime
     rng = np.random.default_rng(7000 + seed)
@@ -285,6 +290,11 @@ def synth_extreme(tables: cfg.NetTables, seed: int, regime: str, rows=None, q_sp
             set_q(l, np.full(L.N, min(int(qi.max()) + 10, 14) if boosted else max(int(qi.max()) - 8, 0)))
             lev = rng.integers(0, 4, size=(L.N, fan))
             zero = rng.random((L.N, fan)) < 0.05
+        elif regime == "wrap2":
+            boosted = qi.max() < 8
+            set_q(l, np.full(L.N, min(int(qi.max()) + 10, 14) if boosted else max(int(qi.max()) - 8, 0)))
+            lev = np.where(rng.random((L.N, fan)) < 0.5, rng.integers(0, 4, size=(L.N, fan)), rng.integers(13, 15, size=(L.N, fan)))
+            zero = rng.random((L.N, fan)) < 0.05
         elif regime == "expand32":
             if L.src >= 0 and L.src in qpos and L.src not in targets:
                 for m in group[L.src]:
@@ -318,6 +328,8 @@ def synth_extreme(tables: cfg.NetTables, seed: int, regime: str, rows=None, q_sp
             lev = None
         if lev is not None:
             sign = np.where(rng.random((L.N, fan)) < 0.5, -1.0, 1.0)
+            if regime == "wrap2":
+                sign[0::4] = 1.0; sign[2::8] = -1.0                # same-sign rows
             w = np.ldexp(sign, -lev)
             w[zero] = 0.0
             model[o["w"]:o["w"] + L.N * fan] = w.astype(np.float32).ravel()
@@ -328,7 +340,7 @@ def synth_extreme(tables: cfg.NetTables, seed: int, regime: str, rows=None, q_sp
             continue
         n = np.arange(L.N)
         mean = np.zeros(L.N); var = np.ones(L.N)
-        if regime == "wrap":
+        if regime in ("wrap", "wrap2"):
             semi = boosted and l % 2 == 0
             gamma = np.ldexp(rng.uniform(1.0, 4.0, L.N), -9) if semi else rng.uniform(1.0, 4.0, L.N)
             beta = rng.uniform(-0.5, 0.5, L.N)
