@@ -520,6 +520,54 @@ tf2_status tf2_emb_roc_pairs(const float* rows_dev, int n_rows, int d, const int
                              int64_t* hist_dev /* [n_folds][2][n_thr+1], ACCUMULATED */, int64_t* invalid_dev /* [1], ACCUMULATED */,
                              void* hip_stream);
 
+/* ---- Activation audit on the device (the integer side of Quantization/debug/CompareError.py; INTEGRATION.md "Activation audit on the
+ * device") ----
+ * Does a Q file fit the integer engine?  An audit handle reduces every kept map of a keep_all step to exact per-channel integer
+ * statistics in a caller-owned device buffer, the STORE, accumulated over as many batches as the caller runs or replays: which channels
+ * clip at 127 / -128 and how often, which use three of their eight bits, what the image row's Q0 makes of the input.
+ * tf2_amd.audit.reference_audit is the host statement; the store equals it as integers.
+ *   record     16 little-endian int64 a channel: 0 n (values seen), 1 neg (v < 0), 2 lo_rail (v == -128), 3 hi_rail (v == 127), 4 min
+ *              (empty: 127), 5 max (empty: -128), 6 sum of v, 7 sum of v * v, 8..15 hist[b], b = bit length of |v| (0 for 0, 1 for 1,
+ *              2 for 2..3, ... 7 for 64..127); |v| = 128 is counted in lo_rail alone, so the hist sums to n - lo_rail.
+ *   values     of table row l: the tensor tf2_net_read_layer hands back for l -- after pool, add and global average ([B][N] for an
+ *              end-pool row), in the reference's int8 values: the kernel reads the workspace's own NHWC layout (channel pitch, concat
+ *              slice offset) and undoes the doubled form 2y - 128 of the channels the packed image flags, y = (v + 128) >> 1.
+ *   store      record 0 .. image_c - 1: the network INPUT ("row -1"), taken from the caller's images_dev, dense [B][C][H][W] -- float
+ *              values quantised by the engine's own input rule with 2^Q0, int8 values as they are (the workspace's input tensor may
+ *              hold an x-only or im2col form that does not contain every pixel).  Then rows 0 .. n_layers - 1 in table order, each
+ *              row's N channels contiguous (a concat member is audited on its own slice; pooling and L2Norm rows are rows like any
+ *              other).  tf2_audit_store_size = 128 * (image_c + sum of N); tf2_audit_describe lists (layer, C, H, W, byte offset,
+ *              channels in the doubled form) per row, row -1 first, and needs no device.
+ * tf2_audit_create needs a packed net (TF2_ERR_STATE otherwise) and allocates nothing on the device; the net must outlive the handle
+ * and keep its tables.  tf2_audit_store_init enqueues the empty store (zeros, min 127, max -128).  tf2_audit_run enqueues the
+ * keep_all step of `batch` images -- logits_dev receives the ordinary logits, bit-identical to tf2_net_run -- and behind it, on the
+ * same stream, one kernel for the input record and one for every 64 table rows (a block: 1024 pixels x 256 channels of one row;
+ * 64-bit integer atomics for the non-zero counters).  Integer adds, minima and maxima only: the store is exact and independent of
+ * grid, order and streams.  No allocation, no synchronisation, no host-side state: graph-capturable; the row descriptions travel in
+ * the kernel arguments, the doubled-form flags are read from the bound packed image.
+ * Refusals, before anything is enqueued: null handle / images / workspace / logits / store, batch <= 0 (TF2_ERR_ARG); a net not packed
+ * or not bound to the device (TF2_ERR_STATE); workspace_bytes < tf2_audit_workspace_size (the keep_all plan's size) or store_bytes <
+ * tf2_audit_store_size (TF2_ERR_SIZE); tf2_audit_describe with capacity < n_layers + 1 (TF2_ERR_SIZE, *n set).
+ * tf2_audit_kept enqueues the audit kernels alone, on a workspace whose last step was this batch's keep_all step (tf2_audit_run's,
+ * or tf2_net_run's on a workspace of the keep_all size) and on the images that step received: what the step left there is the
+ * caller's statement, the library cannot check it.  It is how tools/act_audit_time.py times the audit by itself; same refusals. */
+typedef struct tf2_audit tf2_audit;
+typedef struct tf2_audit_row {
+  int32_t layer, C, H, W;           /* layer -1: the input record */
+  int64_t store_offset;             /* bytes, of the row's first record */
+  int32_t n_doubled, reserved;      /* channels of the row stored as 2y - 128 */
+} tf2_audit_row;
+tf2_status tf2_audit_create(tf2_net* net, tf2_audit** out);
+void       tf2_audit_destroy(tf2_audit* a);
+size_t     tf2_audit_store_size(const tf2_audit* a);
+tf2_status tf2_audit_describe(const tf2_audit* a, tf2_audit_row* rows, int capacity, int* n);
+tf2_status tf2_audit_store_init(const tf2_audit* a, void* store_dev, size_t store_bytes, void* hip_stream);
+size_t     tf2_audit_workspace_size(tf2_audit* a, int batch);
+tf2_status tf2_audit_run(tf2_audit* a, const void* images_dev, int images_are_q, int batch, void* workspace_dev, size_t workspace_bytes,
+                         int8_t* logits_dev, void* store_dev, size_t store_bytes, void* hip_stream);
+tf2_status tf2_audit_kept(tf2_audit* a, const void* images_dev, int images_are_q, int batch, void* workspace_dev, size_t workspace_bytes,
+                          void* store_dev, size_t store_bytes, void* hip_stream);
+
 /* ---- Detection accuracy on the device (the PASCAL VOC devkit protocol behind the README's SSD mAP; INTEGRATION.md "Detection accuracy
  * on the device") ----
  * The reference ships no evaluation code (ssd.py: no weights, no dataset, no eval script), so this statement is the canonical one.

@@ -97,6 +97,12 @@ class ClsDesc(C.Structure):
     _fields_ = [("size", C.c_uint32), ("top_k", C.c_int32)]
 
 
+class AuditRow(C.Structure):
+    """tf2_audit_row (include/tf2_amd.h)."""
+    _fields_ = [("layer", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("store_offset", C.c_int64),
+                ("n_doubled", C.c_int32), ("reserved", C.c_int32)]
+
+
 class DetEvalDesc(C.Structure):
     """tf2_det_eval_desc (include/tf2_amd.h)."""
     _fields_ = [("size", C.c_uint32), ("num_classes", C.c_int32), ("top_k", C.c_int32), ("max_gt", C.c_int32),
@@ -224,6 +230,17 @@ def lib() -> C.CDLL:
     L.tf2_det_eval_store_init.argtypes = [vp, vp, sz, vp]
     L.tf2_det_eval_run.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, sz, vp, vp, vp]
     L.tf2_det_eval_summarise.argtypes = [vp, vp, sz, C.c_int, C.POINTER(DetEvalClass), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    L.tf2_audit_create.argtypes = [vp, C.POINTER(vp)]
+    L.tf2_audit_destroy.argtypes = [vp]
+    L.tf2_audit_destroy.restype = None
+    L.tf2_audit_store_size.argtypes = [vp]
+    L.tf2_audit_store_size.restype = sz
+    L.tf2_audit_describe.argtypes = [vp, C.POINTER(AuditRow), C.c_int, C.POINTER(C.c_int)]
+    L.tf2_audit_store_init.argtypes = [vp, vp, sz, vp]
+    L.tf2_audit_workspace_size.argtypes = [vp, C.c_int]
+    L.tf2_audit_workspace_size.restype = sz
+    L.tf2_audit_run.argtypes = [vp, vp, C.c_int, C.c_int, vp, sz, vp, vp, sz, vp]
+    L.tf2_audit_kept.argtypes = [vp, vp, C.c_int, C.c_int, vp, sz, vp, sz, vp]
     _lib = L
     return L
 
@@ -239,7 +256,9 @@ EXPORTED = [
     "tf2_det_eval_create", "tf2_det_eval_destroy", "tf2_det_eval_store_size", "tf2_det_eval_store_init", "tf2_det_eval_run",
     "tf2_det_eval_summarise",
     "tf2_emb_create", "tf2_emb_destroy", "tf2_emb_scratch_size", "tf2_emb_embed", "tf2_emb_match",
-    "tf2_emb_roc_hist", "tf2_emb_roc_pairs"]
+    "tf2_emb_roc_hist", "tf2_emb_roc_pairs",
+    "tf2_audit_create", "tf2_audit_destroy", "tf2_audit_store_size", "tf2_audit_describe", "tf2_audit_store_init",
+    "tf2_audit_workspace_size", "tf2_audit_run", "tf2_audit_kept"]
 
 
 def parse_opts(text: str) -> dict:

@@ -11,6 +11,7 @@
 #include "embed_match.h"
 #include "embed_roc.h"
 #include "roi_crop.h"
+#include "act_audit.h"
 
 using namespace tf2;
 
@@ -19,6 +20,7 @@ struct tf2_ssd { SsdDetector impl; };
 struct tf2_cls { Classifier impl; };
 struct tf2_det_eval { DetEvaluator impl; };
 struct tf2_emb { Matcher impl; };
+struct tf2_audit { Auditor impl; };
 
 #define CHECK_NET(n)                                              \
   if (!(n)) { set_error("null tf2_net handle"); return TF2_ERR_ARG; }
@@ -390,6 +392,54 @@ tf2_status tf2_emb_roc_hist(const float* rows_a_dev, const int32_t* ids_a_dev, i
 tf2_status tf2_emb_roc_pairs(const float* rows_dev, int n_rows, int d, const int32_t* pairs_dev, int n_pairs, int n_folds, int n_thr,
                              float step, float* dist_dev, int64_t* hist_dev, int64_t* invalid_dev, void* stream) {
   return emb_roc_pairs(rows_dev, n_rows, d, pairs_dev, n_pairs, n_folds, n_thr, step, dist_dev, hist_dev, invalid_dev, stream);
+}
+
+tf2_status tf2_audit_create(tf2_net* net, tf2_audit** out) {
+  CHECK_NET(net);
+  if (!out) { set_error("tf2_audit_create: null argument"); return TF2_ERR_ARG; }
+  tf2_audit* a = new (std::nothrow) tf2_audit();
+  if (!a) { set_error("out of memory"); return TF2_ERR_SIZE; }
+  const tf2_status st = a->impl.create(&net->impl);
+  if (st != TF2_OK) { delete a; return st; }
+  *out = a;
+  return TF2_OK;
+}
+
+void tf2_audit_destroy(tf2_audit* a) { delete a; }
+
+size_t tf2_audit_store_size(const tf2_audit* a) { return a ? a->impl.store_size() : 0; }
+
+tf2_status tf2_audit_describe(const tf2_audit* a, tf2_audit_row* rows, int capacity, int* n) {
+  if (!a) { set_error("null tf2_audit handle"); return TF2_ERR_ARG; }
+  if (!n || (capacity > 0 && !rows)) { set_error("tf2_audit_describe: null argument"); return TF2_ERR_ARG; }
+  const auto& v = a->impl.rows;
+  *n = (int)v.size();
+  if ((int)v.size() > capacity) { set_error("tf2_audit_describe: " + std::to_string(v.size()) + " rows, capacity " + std::to_string(capacity)); return TF2_ERR_SIZE; }
+  for (size_t i = 0; i < v.size(); i++) {
+    rows[i].layer = v[i].layer; rows[i].C = v[i].C; rows[i].H = v[i].H; rows[i].W = v[i].W;
+    rows[i].store_offset = (int64_t)(v[i].rec0 * kAuditSlots * 8);
+    rows[i].n_doubled = v[i].n_doubled; rows[i].reserved = 0;
+  }
+  return TF2_OK;
+}
+
+tf2_status tf2_audit_store_init(const tf2_audit* a, void* store_dev, size_t store_bytes, void* hip_stream) {
+  if (!a) { set_error("null tf2_audit handle"); return TF2_ERR_ARG; }
+  return a->impl.store_init(store_dev, store_bytes, hip_stream);
+}
+
+size_t tf2_audit_workspace_size(tf2_audit* a, int batch) { return a ? a->impl.workspace_size(batch) : 0; }
+
+tf2_status tf2_audit_run(tf2_audit* a, const void* images_dev, int images_are_q, int batch, void* ws, size_t ws_bytes, int8_t* logits_dev,
+                         void* store_dev, size_t store_bytes, void* hip_stream) {
+  if (!a) { set_error("null tf2_audit handle"); return TF2_ERR_ARG; }
+  return a->impl.run(images_dev, images_are_q != 0, batch, ws, ws_bytes, logits_dev, store_dev, store_bytes, hip_stream);
+}
+
+tf2_status tf2_audit_kept(tf2_audit* a, const void* images_dev, int images_are_q, int batch, void* ws, size_t ws_bytes, void* store_dev,
+                          size_t store_bytes, void* hip_stream) {
+  if (!a) { set_error("null tf2_audit handle"); return TF2_ERR_ARG; }
+  return a->impl.run(images_dev, images_are_q != 0, batch, ws, ws_bytes, nullptr, store_dev, store_bytes, hip_stream, false);
 }
 
 tf2_status tf2_det_eval_create(const tf2_det_eval_desc* d, tf2_det_eval** out) {
