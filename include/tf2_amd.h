@@ -568,6 +568,64 @@ tf2_status tf2_audit_run(tf2_audit* a, const void* images_dev, int images_are_q,
 tf2_status tf2_audit_kept(tf2_audit* a, const void* images_dev, int images_are_q, int batch, void* workspace_dev, size_t workspace_bytes,
                           void* store_dev, size_t store_bytes, void* hip_stream);
 
+/* ---- Layer fidelity on the device (Quantization/debug/CompareError.py and Verify(), network_helper.cpp:18-141, for every row;
+ * INTEGRATION.md "Layer fidelity on the device") ----
+ * How far is each channel of each layer from the float network?  A fidelity handle sets every kept int8 map of a keep_all step
+ * against the float32 map of a float forward (tf2_amd.calibrate.float_forward, or any other producer) and keeps exact per-channel
+ * integer statistics in a caller-owned device buffer, the STORE, accumulated over as many batches as the caller runs or replays.
+ * tf2_amd.fidelity.reference_compare is the host statement; the store equals it as integers.
+ *   per value  v: the int8 value tf2_net_read_layer hands back for row l at (b, c, h, w), the doubled form 2y - 128 undone as in the
+ *              audit.  f: the float32 reference at the same (b, c, h, w).  Q: the channel's scale exponent, Verify's for that row
+ *              (1 << -q[l + 1][c] in the runtime table; a pooling row, ipool == 1, carries its source's), any integer in -64 .. 64.
+ *              In this order:  f is NaN or +-inf: nonfinite += 1 and nothing else.  t = f * 2^(Q + 8), ONE float32 multiplication
+ *              (exact unless it overflows to +-inf).  |t| >= 65536: e = +-65536 with t's sign, ref_clamped += 1.  Otherwise
+ *              e = rint(t), half to even (65535.5 -> 65536, not counted as clamped).  d = 256 v - e, so |d| < 2^17.
+ *              k = min(7, bit_length((|d| + 128) >> 8)): the error in whole LSBs after rounding; k = 0: v is the nearest int8.
+ *   record     18 little-endian int64 a channel: 0 n (finite f), 1 nonfinite, 2 ref_clamped, 3 max_abs_d (a maximum; 0 when empty),
+ *              4 sum_d (signed), 5 sum_abs_d, 6 sum_d2, 7 sum_abs_e, 8 sum_e2, 9 sum_q2 = sum of (256 v)^2, 10..17 hist[k].  Every
+ *              slot but 3 is a sum; the empty store is all zeros; two stores combine by adding, slot 3 by the maximum.
+ *   budget     d^2 < 2^34: sum_d2 holds 2^29 values a channel even if every value were wrong by the full range; e^2 <= 2^32 and
+ *              (256 v)^2 <= 2^30 hold more.
+ *   store      the audit's layout: record 0 .. image_c - 1 the network INPUT ("row -1"), then rows 0 .. n_layers - 1 in table order,
+ *              each row's N channels contiguous.  tf2_fid_store_size = 144 * (image_c + sum of N); tf2_fid_describe lists the rows as
+ *              tf2_audit_describe does (store_offset in bytes of THIS store) and needs no device.  Row -1 compares float images with
+ *              their own quantisation: v = the engine's input rule on f with 2^Q0, e from the same f with Q0; with int8 images
+ *              (images_are_q) the row is not compared and its records stay as they are.
+ *   scales     the kernels read 2^(Q + 8) per record from a device table of tf2_fid_store_size / 144 float32 the CALLER keeps:
+ *              tf2_fid_scales writes the table to host memory (no device needed), the caller uploads it once (the handle owns no
+ *              device memory and a run allocates none).  What scales_dev holds is the caller's statement.
+ *   refs       a HOST array of n_layers device pointers, refs[l] the reference of row l: dense float32 [batch][C][H][W] with the
+ *              row's C, H, W of tf2_fid_describe ([batch][C] for an end-pool row) -- a concat member is its own slice.  Each buffer
+ *              must hold batch * C * H * W floats: the library cannot check device sizes.  refs[l] == NULL: row l is not compared,
+ *              costs no block and keeps its records.  The pointers are read at enqueue and travel in the kernel arguments: a
+ *              captured graph replays on the same buffers, refilled.
+ * tf2_fid_create needs a packed net with its q table set (TF2_ERR_STATE otherwise; TF2_ERR_UNSUPPORTED where 2^(Q + 8) is no normal
+ * float32) and allocates nothing on the device; the net must outlive the handle and keep its tables and q.  tf2_fid_store_init
+ * enqueues the empty store (zeros).  tf2_fid_run enqueues the keep_all step of `batch` images -- logits_dev receives the ordinary
+ * logits, bit-identical to tf2_net_run -- and behind it, on the same stream, one kernel for the input record (float images) and one
+ * for every 64 compared rows (a block: 1024 pixels x 64 channels of one row, the float side transposed through LDS; 64-bit integer
+ * atomics for the non-zero counters, a 64-bit atomic maximum for slot 3).  Integer adds and maxima only: the store is exact and
+ * independent of grid, order and streams.  No allocation, no synchronisation, no host state read at replay: graph-capturable.
+ * tf2_fid_kept enqueues the comparison alone, on a workspace whose last step was this batch's keep_all step and on the images that
+ * step received (as tf2_audit_kept; tools/fidelity_time.py times it).
+ * Refusals, before anything is enqueued: null handle / images / workspace / logits / store / refs / scales, batch <= 0
+ * (TF2_ERR_ARG); a net not packed or not bound to the device (TF2_ERR_STATE); workspace_bytes < tf2_fid_workspace_size (the keep_all
+ * plan's size) or store_bytes < tf2_fid_store_size (TF2_ERR_SIZE); tf2_fid_describe with capacity < n_layers + 1 and tf2_fid_scales
+ * with capacity < the records (TF2_ERR_SIZE, *n set). */
+typedef struct tf2_fid tf2_fid;
+tf2_status tf2_fid_create(tf2_net* net, tf2_fid** out);
+void       tf2_fid_destroy(tf2_fid* f);
+size_t     tf2_fid_store_size(const tf2_fid* f);
+tf2_status tf2_fid_describe(const tf2_fid* f, tf2_audit_row* rows, int capacity, int* n);
+tf2_status tf2_fid_scales(const tf2_fid* f, float* scales /* host */, int capacity, int* n);
+tf2_status tf2_fid_store_init(const tf2_fid* f, void* store_dev, size_t store_bytes, void* hip_stream);
+size_t     tf2_fid_workspace_size(tf2_fid* f, int batch);
+tf2_status tf2_fid_run(tf2_fid* f, const void* images_dev, int images_are_q, int batch, void* workspace_dev, size_t workspace_bytes,
+                       int8_t* logits_dev, const float* const* refs /* host array [n_layers] of device pointers */,
+                       const float* scales_dev, void* store_dev, size_t store_bytes, void* hip_stream);
+tf2_status tf2_fid_kept(tf2_fid* f, const void* images_dev, int images_are_q, int batch, void* workspace_dev, size_t workspace_bytes,
+                        const float* const* refs, const float* scales_dev, void* store_dev, size_t store_bytes, void* hip_stream);
+
 /* ---- Detection accuracy on the device (the PASCAL VOC devkit protocol behind the README's SSD mAP; INTEGRATION.md "Detection accuracy
  * on the device") ----
  * The reference ships no evaluation code (ssd.py: no weights, no dataset, no eval script), so this statement is the canonical one.

@@ -241,6 +241,18 @@ def lib() -> C.CDLL:
     L.tf2_audit_workspace_size.restype = sz
     L.tf2_audit_run.argtypes = [vp, vp, C.c_int, C.c_int, vp, sz, vp, vp, sz, vp]
     L.tf2_audit_kept.argtypes = [vp, vp, C.c_int, C.c_int, vp, sz, vp, sz, vp]
+    L.tf2_fid_create.argtypes = [vp, C.POINTER(vp)]
+    L.tf2_fid_destroy.argtypes = [vp]
+    L.tf2_fid_destroy.restype = None
+    L.tf2_fid_store_size.argtypes = [vp]
+    L.tf2_fid_store_size.restype = sz
+    L.tf2_fid_describe.argtypes = [vp, C.POINTER(AuditRow), C.c_int, C.POINTER(C.c_int)]
+    L.tf2_fid_scales.argtypes = [vp, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
+    L.tf2_fid_store_init.argtypes = [vp, vp, sz, vp]
+    L.tf2_fid_workspace_size.argtypes = [vp, C.c_int]
+    L.tf2_fid_workspace_size.restype = sz
+    L.tf2_fid_run.argtypes = [vp, vp, C.c_int, C.c_int, vp, sz, vp, C.POINTER(vp), vp, vp, sz, vp]
+    L.tf2_fid_kept.argtypes = [vp, vp, C.c_int, C.c_int, vp, sz, C.POINTER(vp), vp, vp, sz, vp]
     _lib = L
     return L
 
@@ -258,7 +270,9 @@ EXPORTED = [
     "tf2_emb_create", "tf2_emb_destroy", "tf2_emb_scratch_size", "tf2_emb_embed", "tf2_emb_match",
     "tf2_emb_roc_hist", "tf2_emb_roc_pairs",
     "tf2_audit_create", "tf2_audit_destroy", "tf2_audit_store_size", "tf2_audit_describe", "tf2_audit_store_init",
-    "tf2_audit_workspace_size", "tf2_audit_run", "tf2_audit_kept"]
+    "tf2_audit_workspace_size", "tf2_audit_run", "tf2_audit_kept",
+    "tf2_fid_create", "tf2_fid_destroy", "tf2_fid_store_size", "tf2_fid_describe", "tf2_fid_scales", "tf2_fid_store_init",
+    "tf2_fid_workspace_size", "tf2_fid_run", "tf2_fid_kept"]
 
 
 def parse_opts(text: str) -> dict:

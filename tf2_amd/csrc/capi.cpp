@@ -12,6 +12,7 @@
 #include "embed_roc.h"
 #include "roi_crop.h"
 #include "act_audit.h"
+#include "act_fidelity.h"
 
 using namespace tf2;
 
@@ -21,6 +22,7 @@ struct tf2_cls { Classifier impl; };
 struct tf2_det_eval { DetEvaluator impl; };
 struct tf2_emb { Matcher impl; };
 struct tf2_audit { Auditor impl; };
+struct tf2_fid { Comparator impl; };
 
 #define CHECK_NET(n)                                              \
   if (!(n)) { set_error("null tf2_net handle"); return TF2_ERR_ARG; }
@@ -440,6 +442,64 @@ tf2_status tf2_audit_kept(tf2_audit* a, const void* images_dev, int images_are_q
                           size_t store_bytes, void* hip_stream) {
   if (!a) { set_error("null tf2_audit handle"); return TF2_ERR_ARG; }
   return a->impl.run(images_dev, images_are_q != 0, batch, ws, ws_bytes, nullptr, store_dev, store_bytes, hip_stream, false);
+}
+
+tf2_status tf2_fid_create(tf2_net* net, tf2_fid** out) {
+  CHECK_NET(net);
+  if (!out) { set_error("tf2_fid_create: null argument"); return TF2_ERR_ARG; }
+  tf2_fid* f = new (std::nothrow) tf2_fid();
+  if (!f) { set_error("out of memory"); return TF2_ERR_SIZE; }
+  const tf2_status st = f->impl.create(&net->impl);
+  if (st != TF2_OK) { delete f; return st; }
+  *out = f;
+  return TF2_OK;
+}
+
+void tf2_fid_destroy(tf2_fid* f) { delete f; }
+
+size_t tf2_fid_store_size(const tf2_fid* f) { return f ? f->impl.store_size() : 0; }
+
+tf2_status tf2_fid_describe(const tf2_fid* f, tf2_audit_row* rows, int capacity, int* n) {
+  if (!f) { set_error("null tf2_fid handle"); return TF2_ERR_ARG; }
+  if (!n || (capacity > 0 && !rows)) { set_error("tf2_fid_describe: null argument"); return TF2_ERR_ARG; }
+  const auto& v = f->impl.aud.rows;
+  *n = (int)v.size();
+  if ((int)v.size() > capacity) { set_error("tf2_fid_describe: " + std::to_string(v.size()) + " rows, capacity " + std::to_string(capacity)); return TF2_ERR_SIZE; }
+  for (size_t i = 0; i < v.size(); i++) {
+    rows[i].layer = v[i].layer; rows[i].C = v[i].C; rows[i].H = v[i].H; rows[i].W = v[i].W;
+    rows[i].store_offset = (int64_t)(v[i].rec0 * kFidSlots * 8);
+    rows[i].n_doubled = v[i].n_doubled; rows[i].reserved = 0;
+  }
+  return TF2_OK;
+}
+
+tf2_status tf2_fid_scales(const tf2_fid* f, float* scales, int capacity, int* n) {
+  if (!f) { set_error("null tf2_fid handle"); return TF2_ERR_ARG; }
+  if (!n || (capacity > 0 && !scales)) { set_error("tf2_fid_scales: null argument"); return TF2_ERR_ARG; }
+  const auto& v = f->impl.scale;
+  *n = (int)v.size();
+  if ((int)v.size() > capacity) { set_error("tf2_fid_scales: " + std::to_string(v.size()) + " records, capacity " + std::to_string(capacity)); return TF2_ERR_SIZE; }
+  std::copy(v.begin(), v.end(), scales);
+  return TF2_OK;
+}
+
+tf2_status tf2_fid_store_init(const tf2_fid* f, void* store_dev, size_t store_bytes, void* hip_stream) {
+  if (!f) { set_error("null tf2_fid handle"); return TF2_ERR_ARG; }
+  return f->impl.store_init(store_dev, store_bytes, hip_stream);
+}
+
+size_t tf2_fid_workspace_size(tf2_fid* f, int batch) { return f ? f->impl.workspace_size(batch) : 0; }
+
+tf2_status tf2_fid_run(tf2_fid* f, const void* images_dev, int images_are_q, int batch, void* ws, size_t ws_bytes, int8_t* logits_dev,
+                       const float* const* refs, const float* scales_dev, void* store_dev, size_t store_bytes, void* hip_stream) {
+  if (!f) { set_error("null tf2_fid handle"); return TF2_ERR_ARG; }
+  return f->impl.run(images_dev, images_are_q != 0, batch, ws, ws_bytes, logits_dev, store_dev, store_bytes, refs, scales_dev, hip_stream);
+}
+
+tf2_status tf2_fid_kept(tf2_fid* f, const void* images_dev, int images_are_q, int batch, void* ws, size_t ws_bytes,
+                        const float* const* refs, const float* scales_dev, void* store_dev, size_t store_bytes, void* hip_stream) {
+  if (!f) { set_error("null tf2_fid handle"); return TF2_ERR_ARG; }
+  return f->impl.run(images_dev, images_are_q != 0, batch, ws, ws_bytes, nullptr, store_dev, store_bytes, refs, scales_dev, hip_stream, false);
 }
 
 tf2_status tf2_det_eval_create(const tf2_det_eval_desc* d, tf2_det_eval** out) {
