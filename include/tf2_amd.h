@@ -626,6 +626,52 @@ tf2_status tf2_fid_run(tf2_fid* f, const void* images_dev, int images_are_q, int
 tf2_status tf2_fid_kept(tf2_fid* f, const void* images_dev, int images_are_q, int batch, void* workspace_dev, size_t workspace_bytes,
                         const float* const* refs, const float* scales_dev, void* store_dev, size_t store_bytes, void* hip_stream);
 
+/* ---- INQ weight quantisation on the device (TransForm_Kit/Compression/compress_net/core/compress_core.py: ComputeQuantumRange,
+ * ShapeIntoTwoPower; INTEGRATION.md "Weight quantisation on the device") ----
+ * The engine computes on weights that are 0 or +-2^-i (tf2_get_real reads anything else as +-1 or 0, silently).  tf2_inq_step makes
+ * such weights from float ones by the reference's incremental rule: of every tensor's still-float weights the largest become powers of
+ * two (the caller retrains the rest and calls again with a larger portion).  One call works on many tensors -- SEGMENTS (offset, count
+ * in elements) of one flat float32 device buffer -- in place, with a parallel uint8 mask buffer (non-zero: still float, 0: quantised).
+ * Elements in no segment are never read or written.  tf2_amd.inq.reference_range / reference_step are the host statement; weights,
+ * masks, codes and every word of the state equal it as bits.  All arithmetic is on float32 bit patterns, mag = bits & 0x7fffffff:
+ *   exp_of     of mag > 0: the e with 0.75 * 2^e <= a < 1.5 * 2^e (the reference's floor(log(4a/3) / log 2)): E + 1 where the mantissa
+ *              field is >= 0x400000, else E; denormals by the same inequality from the leading bit.  (The reference's double log gives
+ *              E at a = 1.5 * 2^E exactly for 20 values of E, all <= -30; the integer rule gives E + 1 there as everywhere.)
+ *   range      n1 / n0 = still-float / quantised weights, max1 / max0 the largest mag of each set.  n1 == 0: max_exp = -100, nothing to
+ *              do.  max0 == 0 (nothing, or only zeros, fixed so far): max_exp = exp_of(max1), or -100 with TF2_INQ_ALL_ZERO where max1 is
+ *              0 too.  Otherwise max_exp = the leading-bit exponent of max0 (a power of two), and exp_of(max1) > max_exp sets
+ *              TF2_INQ_RANGE_GREW (the reference exits there).  A NaN or inf anywhere in the tensor: TF2_INQ_NONFINITE, max_exp -100.
+ *              min_exp = max_exp - n_values + 1.  A tensor with a status bit is left untouched: n_keep = n1, n_update = 0.
+ *   rank       n_keep = rint(rint(n1 / (1 - prev)) * (1 - cur)) in double, half to even; n_update = n1 - n_keep; nothing changes when
+ *              n_update <= 0.  thr = the mag of index n_keep in the ascending order of mag over the still-float weights.
+ *   shape      a still-float weight with mag >= thr (every tie included) gets mask 0 and, with e = min(exp_of(mag), 127): +-2^e with
+ *              its sign where e >= min_exp and e >= exp_floor, else +0.0 (flushed_min counts e < min_exp, flushed_floor the others; a
+ *              selected +-0 becomes +0.0 and counts in neither).  over_one counts the weights emitted with e > 0, which the engine
+ *              cannot represent.  exp_floor = -127 is the reference's behaviour, -14 the engine's smallest weight.
+ *   codes      optional, one byte an element of a segment (codes_dev parallel to weights_dev), the 4-bit file's code relative to THIS
+ *              step's min_exp: 15 for a still-float weight, 7 for zero, k = e - min_exp for a negative and k + 8 for a positive power of
+ *              two, 15 where k is outside 0..6.  hist[16] counts them over the whole segment, with or without codes_dev.
+ *   state      32 little-endian int64 a segment, rewritten by every call: 0 n1, 1 n0, 2 max1, 3 max0 (patterns), 4 non-finite count,
+ *              5 max_exp, 6 min_exp, 7 n_keep, 8 n_update, 9 thr (pattern; 0 when nothing is updated), 10 status, 11 flushed_min,
+ *              12 flushed_floor, 13 over_one, 14..29 hist[16], 30..31 zero.  tf2_inq_state_size = 256 * n_segs.
+ * A call enqueues, for every 96 segments: the range kernel, four select passes (an exact radix select of the rank-n_keep pattern:
+ * block-local LDS histograms of 8, 8, 8 and 7 bits, integer atomics, the prefix resolved on the device in between) and the shape
+ * kernel; before them one kernel that zeroes state and scratch.  No host copy, no synchronisation, no allocation, grids that depend
+ * on the host arguments alone: graph-capturable, and a replay on refilled weights and masks equals a fresh call.  Integer adds,
+ * maxima and plain stores only: the result does not depend on grid or order.
+ * Refusals, before anything is enqueued (no device needed): null weights / mask / segs / state / scratch, n_segs < 1, a table that does
+ * not ascend without overlap inside n_total or has a count outside 1 .. 2^31 - 1, prev outside [0, 1), cur outside [prev, 1], n_values
+ * outside 1..15, exp_floor outside -150..127, state or scratch not 8-byte aligned (TF2_ERR_ARG); scratch_bytes <
+ * tf2_inq_scratch_size (TF2_ERR_SIZE).  16-byte accesses are used where weights_dev is 16-byte and mask_dev / codes_dev are 4-byte
+ * aligned (any alignment is correct). */
+enum { TF2_INQ_RANGE_GREW = 1, TF2_INQ_ALL_ZERO = 2, TF2_INQ_NONFINITE = 4 };
+typedef struct tf2_inq_seg { int64_t offset, count; } tf2_inq_seg;     /* elements of the flat buffer */
+size_t     tf2_inq_scratch_size(int n_segs);
+size_t     tf2_inq_state_size(int n_segs);
+tf2_status tf2_inq_step(float* weights_dev, uint8_t* mask_dev, int64_t n_total, const tf2_inq_seg* segs /* host */, int n_segs,
+                        double prev, double cur, int n_values, int exp_floor, uint8_t* codes_dev /* or NULL */, void* state_dev,
+                        void* scratch_dev, size_t scratch_bytes, void* hip_stream);
+
 /* ---- Detection accuracy on the device (the PASCAL VOC devkit protocol behind the README's SSD mAP; INTEGRATION.md "Detection accuracy
  * on the device") ----
  * The reference ships no evaluation code (ssd.py: no weights, no dataset, no eval script), so this statement is the canonical one.

@@ -103,6 +103,11 @@ class AuditRow(C.Structure):
                 ("n_doubled", C.c_int32), ("reserved", C.c_int32)]
 
 
+class InqSeg(C.Structure):
+    """tf2_inq_seg (include/tf2_amd.h): a tensor of the flat weight buffer, in elements."""
+    _fields_ = [("offset", C.c_int64), ("count", C.c_int64)]
+
+
 class DetEvalDesc(C.Structure):
     """tf2_det_eval_desc (include/tf2_amd.h)."""
     _fields_ = [("size", C.c_uint32), ("num_classes", C.c_int32), ("top_k", C.c_int32), ("max_gt", C.c_int32),
@@ -253,6 +258,11 @@ def lib() -> C.CDLL:
     L.tf2_fid_workspace_size.restype = sz
     L.tf2_fid_run.argtypes = [vp, vp, C.c_int, C.c_int, vp, sz, vp, C.POINTER(vp), vp, vp, sz, vp]
     L.tf2_fid_kept.argtypes = [vp, vp, C.c_int, C.c_int, vp, sz, C.POINTER(vp), vp, vp, sz, vp]
+    L.tf2_inq_scratch_size.argtypes = [C.c_int]
+    L.tf2_inq_scratch_size.restype = sz
+    L.tf2_inq_state_size.argtypes = [C.c_int]
+    L.tf2_inq_state_size.restype = sz
+    L.tf2_inq_step.argtypes = [vp, vp, C.c_int64, C.POINTER(InqSeg), C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, vp, vp, vp, sz, vp]
     _lib = L
     return L
 
@@ -272,7 +282,8 @@ EXPORTED = [
     "tf2_audit_create", "tf2_audit_destroy", "tf2_audit_store_size", "tf2_audit_describe", "tf2_audit_store_init",
     "tf2_audit_workspace_size", "tf2_audit_run", "tf2_audit_kept",
     "tf2_fid_create", "tf2_fid_destroy", "tf2_fid_store_size", "tf2_fid_describe", "tf2_fid_scales", "tf2_fid_store_init",
-    "tf2_fid_workspace_size", "tf2_fid_run", "tf2_fid_kept"]
+    "tf2_fid_workspace_size", "tf2_fid_run", "tf2_fid_kept",
+    "tf2_inq_scratch_size", "tf2_inq_state_size", "tf2_inq_step"]
 
 
 def parse_opts(text: str) -> dict:

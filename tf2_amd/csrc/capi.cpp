@@ -13,6 +13,7 @@
 #include "roi_crop.h"
 #include "act_audit.h"
 #include "act_fidelity.h"
+#include "weight_inq.h"
 
 using namespace tf2;
 
@@ -500,6 +501,17 @@ tf2_status tf2_fid_kept(tf2_fid* f, const void* images_dev, int images_are_q, in
                         const float* const* refs, const float* scales_dev, void* store_dev, size_t store_bytes, void* hip_stream) {
   if (!f) { set_error("null tf2_fid handle"); return TF2_ERR_ARG; }
   return f->impl.run(images_dev, images_are_q != 0, batch, ws, ws_bytes, nullptr, store_dev, store_bytes, refs, scales_dev, hip_stream, false);
+}
+
+size_t tf2_inq_scratch_size(int n_segs) { return n_segs < 1 ? 0 : inq_scratch_size(n_segs); }
+
+size_t tf2_inq_state_size(int n_segs) { return n_segs < 1 ? 0 : inq_state_size(n_segs); }
+
+tf2_status tf2_inq_step(float* weights_dev, uint8_t* mask_dev, int64_t n_total, const tf2_inq_seg* segs, int n_segs, double prev, double cur,
+                        int n_values, int exp_floor, uint8_t* codes_dev, void* state_dev, void* scratch_dev, size_t scratch_bytes,
+                        void* hip_stream) {
+  return inq_step(weights_dev, mask_dev, n_total, segs, n_segs, prev, cur, n_values, exp_floor, codes_dev, state_dev, scratch_dev,
+                  scratch_bytes, hip_stream);
 }
 
 tf2_status tf2_det_eval_create(const tf2_det_eval_desc* d, tf2_det_eval** out) {
