@@ -672,6 +672,60 @@ tf2_status tf2_inq_step(float* weights_dev, uint8_t* mask_dev, int64_t n_total, 
                         double prev, double cur, int n_values, int exp_floor, uint8_t* codes_dev /* or NULL */, void* state_dev,
                         void* scratch_dev, size_t scratch_bytes, void* hip_stream);
 
+/* ---- Channel pruning on the device (TransForm_Kit/DnsChannelpruning: dnscp_core.py cal_mean_std / maskChannelCalc, model_convert.py;
+ * INTEGRATION.md "Channel pruning on the device") ----
+ * DNS-CP prunes INPUT channels of a conv [N][C][k][k] whose mean magnitude falls under a threshold taken from the conv's own mean and
+ * deviation, revives them above a higher one, and forces the kept count to a multiple of 16.  tf2_dnscp_step does that for many convs
+ * -- descriptors (host records) over one flat float32 device buffer -- with one keep byte a channel (non-zero: kept) and writes the
+ * masked weights; the dense weights stay the caller's (out_dev may equal dense_dev).  The random gate, the training loop and the
+ * thresholds' arithmetic stay with the caller.  tf2_amd.dnscp.reference_stats / reference_step are the host statement; keep bytes, the
+ * output, S1 and every word of the record equal it as bits.  Float sums have no defined order, so the rule is stated on bit patterns:
+ *   fixed point  E = the leading-bit exponent of the conv's largest FINITE magnitude (denormals from the leading bit; -1000 for none);
+ *                m(a) = floor(a * 2^(31 - E)), 0 <= m < 2^32, a shift of the significand; m = 0 for a non-finite pattern.
+ *   sums         S1[c] = sum of m over input channel c (dense).  Over the channels kept at entry: A1 = sum m, A2_hi = sum (m^2 >> 32),
+ *                A2_lo = sum (m^2 & 0xffffffff), nz = the patterns with mag != 0; n = N * C * kk.  Exact for N * kk < 2^22, n < 2^28.
+ *   thresholds   host arithmetic (tf2_amd.dnscp.thresholds: mu = A1 / nz, var = (A2 - n mu^2) / n, T = max(mu + c_rate * sqrt(var), 0),
+ *                t_lo = alpha_low * T, t_hi = alpha_high * T in the weights' units), handed in by the descriptor; >= 0 or NaN.
+ *   compare      B = floor(t * double(N * kk) * 2^(31 - max(E, -149))): one IEEE multiply, an exact scaling, a floor, clamped to
+ *                [-1, 2^63 - 1]; a NaN t_lo gives B_lo = -1, a NaN t_hi B_hi = 2^63 - 1 (nothing changes) and TF2_DNSCP_NAN_THRESHOLD.
+ *                A kept channel with S1[c] <= B_lo is pruned, a pruned one with S1[c] > B_hi revived.
+ *   fix-up       nz_c kept channels behind the compare; target = 16 * rint(nz_c / 16) (half to even), 16 where that is 0.  The first
+ *                pruned channels by index are revived, or the first kept ones pruned, until the count is the target or C runs out.
+ *   output       out = dense where the channel is kept, else the pattern 0x00000000 (the reference's multiply leaves -0.0 for a
+ *                negative weight; tf2_get_real reads both as zero).  Convs without TF2_DNSCP_UPDATE get their keep bytes applied as
+ *                they are.  A conv holding a NaN or inf: TF2_DNSCP_NONFINITE, its keep bytes and its part of out_dev left as they were.
+ *   record       16 little-endian int64 a conv, rewritten by every call: 0 n, 1 nz, 2 non-finite count, 3 max pattern, 4 E, 5 A1,
+ *                6 A2_hi, 7 A2_lo, 8 kept before, 9 pruned by t_lo, 10 revived by t_hi, 11 fix-up (+ revived, - pruned), 12 kept
+ *                after, 13 status, 14 B_lo, 15 B_hi (9..11, 14, 15 are 0 without TF2_DNSCP_UPDATE).  tf2_dnscp_state_size = 128 * n_convs.
+ * keep_dev and sums_dev (int64 S1) are indexed alike: conv i owns [keep_offset, keep_offset + C) of n_channels.  tf2_dnscp_stats writes
+ * the record and S1 only (keep_dev NULL: all kept).  A step enqueues, for every 48 convs: zeroing, the max pass, the sum pass (every
+ * filter read once; 64-bit LDS adds, one 64-bit atomic per channel and block), one decision block a conv, the apply pass.  No host
+ * copy, no synchronisation, no allocation, grids from the host arguments alone: graph-capturable; integer adds and maxima only, so the
+ * result does not depend on grid or order.  tf2_dnscp_scratch_size is 0 with these kernels (scratch_dev may be NULL).
+ * tf2_dnscp_compact is the export (model_convert.py): for every segment dst[n'][c'][j] = src[n_idx[n']][c_idx[c']][j], j < kk, the
+ * index lists int32 in idx_dev at element offsets n_idx / c_idx (-1: identity); an index outside the source tensor writes a NaN.
+ * One launch per 48 segments.
+ * Refusals, before anything is enqueued (no device needed): null dense / out / keep (step) / convs / sums / state, n_convs < 1, sizes
+ * < 1, a conv table or keep ranges that do not ascend without overlap inside n_total / n_channels, unknown flags, TF2_DNSCP_UPDATE in
+ * tf2_dnscp_stats, a negative threshold, out_dev overlapping dense_dev without being equal, state or sums not 8-byte aligned
+ * (TF2_ERR_ARG); C > 4096, N * kk >= 2^22, n >= 2^28 (TF2_ERR_UNSUPPORTED).  tf2_dnscp_compact: null pointers, sizes < 1, a source
+ * tensor outside n_src, destinations that do not ascend without overlap inside n_dst, an index list outside n_idx or an identity
+ * between unequal sizes, dst_dev overlapping src_dev (TF2_ERR_ARG). */
+enum { TF2_DNSCP_UPDATE = 1 };                                                      /* flags */
+enum { TF2_DNSCP_ALL_ZERO = 1, TF2_DNSCP_NONFINITE = 2, TF2_DNSCP_NAN_THRESHOLD = 4 };   /* status */
+typedef struct tf2_dnscp_conv { int64_t offset; int32_t N, C, kk, flags; int64_t keep_offset; double t_lo, t_hi; } tf2_dnscp_conv;
+typedef struct tf2_dnscp_seg { int64_t src_offset, dst_offset; int32_t n_src, c_src, n_out, c_out, kk, reserved; int64_t n_idx, c_idx; } tf2_dnscp_seg;
+size_t     tf2_dnscp_state_size(int n_convs);
+size_t     tf2_dnscp_scratch_size(int n_convs);
+tf2_status tf2_dnscp_stats(const float* weights_dev, int64_t n_total, const tf2_dnscp_conv* convs /* host */, int n_convs,
+                           const uint8_t* keep_dev /* or NULL */, int64_t n_channels, int64_t* sums_dev, void* state_dev,
+                           void* scratch_dev, size_t scratch_bytes, void* hip_stream);
+tf2_status tf2_dnscp_step(const float* dense_dev, float* out_dev, int64_t n_total, const tf2_dnscp_conv* convs /* host */, int n_convs,
+                          uint8_t* keep_dev, int64_t n_channels, int64_t* sums_dev, void* state_dev, void* scratch_dev,
+                          size_t scratch_bytes, void* hip_stream);
+tf2_status tf2_dnscp_compact(const float* src_dev, int64_t n_src, float* dst_dev, int64_t n_dst, const tf2_dnscp_seg* segs /* host */,
+                             int n_segs, const int32_t* idx_dev, int64_t n_idx, void* hip_stream);
+
 /* ---- Detection accuracy on the device (the PASCAL VOC devkit protocol behind the README's SSD mAP; INTEGRATION.md "Detection accuracy
  * on the device") ----
  * The reference ships no evaluation code (ssd.py: no weights, no dataset, no eval script), so this statement is the canonical one.

@@ -108,6 +108,18 @@ class InqSeg(C.Structure):
     _fields_ = [("offset", C.c_int64), ("count", C.c_int64)]
 
 
+class DnscpConv(C.Structure):
+    """tf2_dnscp_conv (include/tf2_amd.h): a conv [N][C][kk] of the flat weight buffer, in elements."""
+    _fields_ = [("offset", C.c_int64), ("N", C.c_int32), ("C", C.c_int32), ("kk", C.c_int32), ("flags", C.c_int32),
+                ("keep_offset", C.c_int64), ("t_lo", C.c_double), ("t_hi", C.c_double)]
+
+
+class DnscpSeg(C.Structure):
+    """tf2_dnscp_seg (include/tf2_amd.h): a tensor of the pruned stream and where it comes from."""
+    _fields_ = [("src_offset", C.c_int64), ("dst_offset", C.c_int64), ("n_src", C.c_int32), ("c_src", C.c_int32), ("n_out", C.c_int32),
+                ("c_out", C.c_int32), ("kk", C.c_int32), ("reserved", C.c_int32), ("n_idx", C.c_int64), ("c_idx", C.c_int64)]
+
+
 class DetEvalDesc(C.Structure):
     """tf2_det_eval_desc (include/tf2_amd.h)."""
     _fields_ = [("size", C.c_uint32), ("num_classes", C.c_int32), ("top_k", C.c_int32), ("max_gt", C.c_int32),
@@ -263,6 +275,13 @@ def lib() -> C.CDLL:
     L.tf2_inq_state_size.argtypes = [C.c_int]
     L.tf2_inq_state_size.restype = sz
     L.tf2_inq_step.argtypes = [vp, vp, C.c_int64, C.POINTER(InqSeg), C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, vp, vp, vp, sz, vp]
+    L.tf2_dnscp_state_size.argtypes = [C.c_int]
+    L.tf2_dnscp_state_size.restype = sz
+    L.tf2_dnscp_scratch_size.argtypes = [C.c_int]
+    L.tf2_dnscp_scratch_size.restype = sz
+    L.tf2_dnscp_stats.argtypes = [vp, C.c_int64, C.POINTER(DnscpConv), C.c_int, vp, C.c_int64, vp, vp, vp, sz, vp]
+    L.tf2_dnscp_step.argtypes = [vp, vp, C.c_int64, C.POINTER(DnscpConv), C.c_int, vp, C.c_int64, vp, vp, vp, sz, vp]
+    L.tf2_dnscp_compact.argtypes = [vp, C.c_int64, vp, C.c_int64, C.POINTER(DnscpSeg), C.c_int, vp, C.c_int64, vp]
     _lib = L
     return L
 
@@ -283,7 +302,8 @@ EXPORTED = [
     "tf2_audit_workspace_size", "tf2_audit_run", "tf2_audit_kept",
     "tf2_fid_create", "tf2_fid_destroy", "tf2_fid_store_size", "tf2_fid_describe", "tf2_fid_scales", "tf2_fid_store_init",
     "tf2_fid_workspace_size", "tf2_fid_run", "tf2_fid_kept",
-    "tf2_inq_scratch_size", "tf2_inq_state_size", "tf2_inq_step"]
+    "tf2_inq_scratch_size", "tf2_inq_state_size", "tf2_inq_step",
+    "tf2_dnscp_state_size", "tf2_dnscp_scratch_size", "tf2_dnscp_stats", "tf2_dnscp_step", "tf2_dnscp_compact"]
 
 
 def parse_opts(text: str) -> dict:

@@ -14,6 +14,7 @@
 #include "act_audit.h"
 #include "act_fidelity.h"
 #include "weight_inq.h"
+#include "weight_dnscp.h"
 
 using namespace tf2;
 
@@ -501,6 +502,27 @@ tf2_status tf2_fid_kept(tf2_fid* f, const void* images_dev, int images_are_q, in
                         const float* const* refs, const float* scales_dev, void* store_dev, size_t store_bytes, void* hip_stream) {
   if (!f) { set_error("null tf2_fid handle"); return TF2_ERR_ARG; }
   return f->impl.run(images_dev, images_are_q != 0, batch, ws, ws_bytes, nullptr, store_dev, store_bytes, refs, scales_dev, hip_stream, false);
+}
+
+size_t tf2_dnscp_state_size(int n_convs) { return n_convs < 1 ? 0 : dnscp_state_size(n_convs); }
+
+size_t tf2_dnscp_scratch_size(int) { return 0; }
+
+tf2_status tf2_dnscp_stats(const float* weights_dev, int64_t n_total, const tf2_dnscp_conv* convs, int n_convs, const uint8_t* keep_dev,
+                           int64_t n_channels, int64_t* sums_dev, void* state_dev, void* scratch_dev, size_t scratch_bytes, void* hip_stream) {
+  return dnscp_run(weights_dev, nullptr, n_total, convs, n_convs, const_cast<uint8_t*>(keep_dev), n_channels, (long long*)sums_dev, state_dev,
+                   scratch_dev, scratch_bytes, hip_stream, false);
+}
+
+tf2_status tf2_dnscp_step(const float* dense_dev, float* out_dev, int64_t n_total, const tf2_dnscp_conv* convs, int n_convs, uint8_t* keep_dev,
+                          int64_t n_channels, int64_t* sums_dev, void* state_dev, void* scratch_dev, size_t scratch_bytes, void* hip_stream) {
+  return dnscp_run(dense_dev, out_dev, n_total, convs, n_convs, keep_dev, n_channels, (long long*)sums_dev, state_dev, scratch_dev,
+                   scratch_bytes, hip_stream, true);
+}
+
+tf2_status tf2_dnscp_compact(const float* src_dev, int64_t n_src, float* dst_dev, int64_t n_dst, const tf2_dnscp_seg* segs, int n_segs,
+                             const int32_t* idx_dev, int64_t n_idx, void* hip_stream) {
+  return dnscp_compact(src_dev, n_src, dst_dev, n_dst, segs, n_segs, idx_dev, n_idx, hip_stream);
 }
 
 size_t tf2_inq_scratch_size(int n_segs) { return n_segs < 1 ? 0 : inq_scratch_size(n_segs); }
