@@ -626,6 +626,58 @@ tf2_status tf2_fid_run(tf2_fid* f, const void* images_dev, int images_are_q, int
 tf2_status tf2_fid_kept(tf2_fid* f, const void* images_dev, int images_are_q, int batch, void* workspace_dev, size_t workspace_bytes,
                         const float* const* refs, const float* scales_dev, void* store_dev, size_t store_bytes, void* hip_stream);
 
+/* ---- CAQ calibration on the device (TransForm_Kit/Quantization/feature_write.py and quantization.py: QuantizeForShift,
+ * QuantizeChannel; INTEGRATION.md "Calibration on the device") ----
+ * The step that makes the Q file: which power-of-two scale keeps each channel of each float map inside int8?  The two passes read the
+ * float32 maps of a float forward (tf2_amd.fidelity.float_refs, or any other producer) once each and keep exact per-channel integer
+ * records in caller-owned device buffers, the STORES, accumulated over as many batches as the caller runs or replays.  They need no
+ * net, no packed image and no Q table: they run before any exists.  tf2_amd.caq.reference_range / reference_error are the host
+ * statement; the stores equal it as integers.  tf2_amd.caq turns host copies of the stores into Q rows (q_max: the reference's rule,
+ * bit for bit; q_clip: a clip-share rule; q_mse: an error-minimising rule).
+ *   fit        of a finite non-zero float32 f: the largest integer q with |f| * 2^q <= 127, stated on the bit pattern: with e the
+ *              unbiased exponent and m the 24-bit significand (a denormal normalised first), fit = 6 - e where m <= 0xFE0000, else
+ *              5 - e.  QuantizeForShift of a non-negative channel is fit of its peak.  The maps are read as 32-bit patterns, so a
+ *              denormal counts as the value it is, whatever the flush mode.
+ *   RANGE      tf2_caq_range, 70 little-endian int64 a channel: 0 n (finite values), 1 nonfinite (NaN, +-inf: nothing else is
+ *              recorded for these), 2 zeros (+-0), 3 negatives (finite, < 0), 4 peak_pos (the magnitude bit pattern of the largest
+ *              positive value, 0 when none), 5 peak_neg (of the most negative value, 0 when none), 6..69 hist[b] with
+ *              b = clamp(fit(f), -32, 31) + 32 over the non-zero finite values.  Slots 4 and 5 are maxima, every other slot is a
+ *              sum; the empty store is all zeros; two stores combine by adding, slots 4 and 5 by the maximum.  The sum of hist[b]
+ *              over b < Q + 32 counts the values beyond the rail at exponent Q.
+ *   ERROR      tf2_caq_error, 12 little-endian int64 a channel, against a base exponent Qb per record, any integer in -64 .. 64: the
+ *              kernel reads 2^(Qb + 7) per record from a device table of float32 the CALLER keeps (tf2_amd.caq.scale_of); what
+ *              scales_dev holds is the caller's statement.  The candidates are Q = Qb + j, j = 0 .. 3 (below Qb = fit(peak) nothing
+ *              clips and the step only coarsens).  Per value, in this order:  f is NaN or +-inf: nonfinite += 1 and nothing else.
+ *              t = f * 2^(Qb + 7), ONE float32 multiplication.  |t| >= 2^18 (an overflow to inf included): e = +-2^18 with t's sign,
+ *              ref_clamped += 1; otherwise e = rint(t), half to even.  For each j, with s = 7 - j: u = (e + (1 << (s - 1))) >> s
+ *              (arithmetic shift), v = clamp(u, -128, 127), clipped_j += (u != v), d = e - (v << s), sum_d2_j += d^2.
+ *              Slots: 0 n, 1 nonfinite, 2 ref_clamped, 3 sum_e2, 4..7 clipped_j, 8..11 sum_d2_j.  Every slot is a sum.
+ *   budget     |d| < 2^18 + 2^14, so d^2 < 2^37: a sum_d2 slot holds 2^26 values a channel even if every value were wrong by the full
+ *              range; e^2 <= 2^36 holds more.
+ *   denormals  with |Qb| <= 64 a denormal input or product gives |t| < 0.5 and e = 0 in either flush mode.
+ *   rows       a HOST array of n_rows descriptors (C, HW, the row's first record) and a HOST array of n_rows device pointers,
+ *              maps[i] the dense float32 [batch][C][HW] map of row i ([batch][C] where HW is 1).  Each buffer must hold
+ *              batch * C * HW floats, 4-byte aligned: the library cannot check device sizes.  maps[i] == NULL: row i is not read,
+ *              costs no block and keeps its records.  The pointers are read at enqueue and travel in the kernel arguments: a
+ *              captured graph replays on the same buffers, refilled.  The audit's record layout is the convention: the network
+ *              input's channels first ("row -1", the float images), then the table rows in order.
+ * The functions are stateless.  A call enqueues one kernel for every 64 observed rows (a block: 32768 values of one channel, walked
+ * through all images in 16-byte groups with a guarded head and tail, the histogram counted per wave by ballot over the distinct bins;
+ * 64-bit integer atomics for the non-zero counters, 64-bit atomic maxima for the peaks).  Integer adds and maxima only: the stores are
+ * exact and independent of grid, order and streams.  No allocation, no synchronisation, no host state read at replay:
+ * graph-capturable.  tf2_caq_store_init enqueues the empty store (zeros) over store_bytes.
+ * Refusals, before anything is enqueued (no device needed): null rows / maps / store / scales, n_rows < 1, batch <= 0, C <= 0,
+ * HW <= 0, a negative first record, record ranges that overlap, a store or map that is not aligned (TF2_ERR_ARG); a row whose records
+ * reach beyond store_bytes (TF2_ERR_SIZE); batch * HW or a record index beyond 2^31 (TF2_ERR_UNSUPPORTED). */
+typedef struct tf2_caq_row { int32_t C, HW; int64_t first_record; } tf2_caq_row;
+size_t     tf2_caq_range_store_size(int64_t n_records);     /* 560 * n_records */
+size_t     tf2_caq_error_store_size(int64_t n_records);     /* 96 * n_records */
+tf2_status tf2_caq_store_init(void* store_dev, size_t store_bytes, void* hip_stream);
+tf2_status tf2_caq_range(const tf2_caq_row* rows /* host */, const void* const* maps /* host array [n_rows] of device pointers */,
+                         int n_rows, int batch, void* store_dev, size_t store_bytes, void* hip_stream);
+tf2_status tf2_caq_error(const tf2_caq_row* rows /* host */, const void* const* maps, int n_rows, int batch, const float* scales_dev,
+                         void* store_dev, size_t store_bytes, void* hip_stream);
+
 /* ---- INQ weight quantisation on the device (TransForm_Kit/Compression/compress_net/core/compress_core.py: ComputeQuantumRange,
  * ShapeIntoTwoPower; INTEGRATION.md "Weight quantisation on the device") ----
  * The engine computes on weights that are 0 or +-2^-i (tf2_get_real reads anything else as +-1 or 0, silently).  tf2_inq_step makes

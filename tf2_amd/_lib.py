@@ -103,6 +103,11 @@ class AuditRow(C.Structure):
                 ("n_doubled", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CaqRow(C.Structure):
+    """tf2_caq_row (include/tf2_amd.h): a row of dense float32 [batch][C][HW] and its first record."""
+    _fields_ = [("C", C.c_int32), ("HW", C.c_int32), ("first_record", C.c_int64)]
+
+
 class InqSeg(C.Structure):
     """tf2_inq_seg (include/tf2_amd.h): a tensor of the flat weight buffer, in elements."""
     _fields_ = [("offset", C.c_int64), ("count", C.c_int64)]
@@ -270,6 +275,13 @@ def lib() -> C.CDLL:
     L.tf2_fid_workspace_size.restype = sz
     L.tf2_fid_run.argtypes = [vp, vp, C.c_int, C.c_int, vp, sz, vp, C.POINTER(vp), vp, vp, sz, vp]
     L.tf2_fid_kept.argtypes = [vp, vp, C.c_int, C.c_int, vp, sz, C.POINTER(vp), vp, vp, sz, vp]
+    L.tf2_caq_range_store_size.argtypes = [C.c_int64]
+    L.tf2_caq_range_store_size.restype = sz
+    L.tf2_caq_error_store_size.argtypes = [C.c_int64]
+    L.tf2_caq_error_store_size.restype = sz
+    L.tf2_caq_store_init.argtypes = [vp, sz, vp]
+    L.tf2_caq_range.argtypes = [C.POINTER(CaqRow), C.POINTER(vp), C.c_int, C.c_int, vp, sz, vp]
+    L.tf2_caq_error.argtypes = [C.POINTER(CaqRow), C.POINTER(vp), C.c_int, C.c_int, vp, vp, sz, vp]
     L.tf2_inq_scratch_size.argtypes = [C.c_int]
     L.tf2_inq_scratch_size.restype = sz
     L.tf2_inq_state_size.argtypes = [C.c_int]
@@ -302,6 +314,7 @@ EXPORTED = [
     "tf2_audit_workspace_size", "tf2_audit_run", "tf2_audit_kept",
     "tf2_fid_create", "tf2_fid_destroy", "tf2_fid_store_size", "tf2_fid_describe", "tf2_fid_scales", "tf2_fid_store_init",
     "tf2_fid_workspace_size", "tf2_fid_run", "tf2_fid_kept",
+    "tf2_caq_range_store_size", "tf2_caq_error_store_size", "tf2_caq_store_init", "tf2_caq_range", "tf2_caq_error",
     "tf2_inq_scratch_size", "tf2_inq_state_size", "tf2_inq_step",
     "tf2_dnscp_state_size", "tf2_dnscp_scratch_size", "tf2_dnscp_stats", "tf2_dnscp_step", "tf2_dnscp_compact"]
 

@@ -13,6 +13,7 @@
 #include "roi_crop.h"
 #include "act_audit.h"
 #include "act_fidelity.h"
+#include "act_caq.h"
 #include "weight_inq.h"
 #include "weight_dnscp.h"
 
@@ -502,6 +503,22 @@ tf2_status tf2_fid_kept(tf2_fid* f, const void* images_dev, int images_are_q, in
                         const float* const* refs, const float* scales_dev, void* store_dev, size_t store_bytes, void* hip_stream) {
   if (!f) { set_error("null tf2_fid handle"); return TF2_ERR_ARG; }
   return f->impl.run(images_dev, images_are_q != 0, batch, ws, ws_bytes, nullptr, store_dev, store_bytes, refs, scales_dev, hip_stream, false);
+}
+
+size_t tf2_caq_range_store_size(int64_t n_records) { return n_records < 1 ? 0 : caq_range_store_size(n_records); }
+
+size_t tf2_caq_error_store_size(int64_t n_records) { return n_records < 1 ? 0 : caq_error_store_size(n_records); }
+
+tf2_status tf2_caq_store_init(void* store_dev, size_t store_bytes, void* hip_stream) { return caq_store_init(store_dev, store_bytes, hip_stream); }
+
+tf2_status tf2_caq_range(const tf2_caq_row* rows, const void* const* maps, int n_rows, int batch, void* store_dev, size_t store_bytes,
+                         void* hip_stream) {
+  return caq_run(false, rows, maps, n_rows, batch, nullptr, store_dev, store_bytes, hip_stream);
+}
+
+tf2_status tf2_caq_error(const tf2_caq_row* rows, const void* const* maps, int n_rows, int batch, const float* scales_dev, void* store_dev,
+                         size_t store_bytes, void* hip_stream) {
+  return caq_run(true, rows, maps, n_rows, batch, scales_dev, store_dev, store_bytes, hip_stream);
 }
 
 size_t tf2_dnscp_state_size(int n_convs) { return n_convs < 1 ? 0 : dnscp_state_size(n_convs); }
