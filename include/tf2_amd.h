@@ -412,6 +412,75 @@ tf2_status tf2_roi_crop(const tf2_net* net2, const tf2_preprocess_desc* d, const
                         const tf2_image_src* srcs_dev, int batch, const tf2_roi* rois_dev, int n_slots, int out_q, void* out_dev,
                         int32_t* status_dev, void* hip_stream);
 
+/* ---- YCbCr frames on the device (INTEGRATION.md "YCbCr frames on the device") ----
+ * The step in front of the three gather calls above: a batch of planar or semi-planar 8-bit YCbCr frames (what a JPEG or a video
+ * decoder leaves) -> the interleaved pixels those calls read, written where their tf2_image_src records point.  Needs no net handle.
+ * Image b has the size h x w, the offset and the row_pitch of srcs_dev[b] (its resize_* and crop_* fields are not read); its planes
+ * are described by ycc_dev[b]; chroma planes are ch = ceil(h / sub_y) rows of cw = ceil(w / sub_x) samples.  All arithmetic is
+ * integer and >> is arithmetic; tf2_amd.ycc.reference is the host statement and the device is bit-identical to it.  With JFIF and
+ * FANCY the result is byte for byte what libjpeg-turbo's decoder (and with it Pillow's) makes of the same planes: "fancy" upsampling
+ * and the jdcolor tables (tests/golden/pil_ycc.npz holds Pillow's own bytes).
+ * Upsampled chroma at output pixel (y, x), for a chroma plane P (Cb and Cr alike):
+ *   REPLICATE                 P[y / sub_y][x / sub_x]
+ *   FANCY, (1,1)              P[y][x]
+ *   FANCY, (2,1)              p = P[y], k = x >> 1;  x even: k == 0 ? p[0] : (3*p[k] + p[k-1] + 1) >> 2
+ *                                                    x odd:  k == cw-1 ? p[k] : (3*p[k] + p[k+1] + 2) >> 2
+ *   FANCY, (2,2)              r = y >> 1, k = x >> 1, o = (y even) ? max(r-1, 0) : min(r+1, ch-1), s[j] = 3*P[r][j] + P[o][j];
+ *                             x even: k == 0 ? (4*s[0] + 8) >> 4 : (3*s[k] + s[k-1] + 8) >> 4
+ *                             x odd:  k == cw-1 ? (4*s[k] + 7) >> 4 : (3*s[k] + s[k+1] + 7) >> 4
+ * Colour, with FIX(v) = (int)(v * 65536 + 0.5), cb = Cb - 128, cr = Cr - 128 and every result clamped to 0..255:
+ *   JFIF (full range)         R = Y + ((FIX(1.40200)*cr + 32768) >> 16)
+ *                             G = Y + ((-FIX(0.34414)*cb + 32768 - FIX(0.71414)*cr) >> 16)
+ *                             B = Y + ((FIX(1.77200)*cb + 32768) >> 16)
+ *   BT601, BT709 (limited)    yy = Y - 16, one sum a channel: (FIX(ky)*yy +- FIX(|a|)*cb +- FIX(|b|)*cr + 32768) >> 16
+ *     BT601: ky 1.164383; R +1.596027 cr; G -0.391762 cb -0.812968 cr; B +2.017232 cb
+ *     BT709: ky 1.164384; R +1.792741 cr; G -0.213249 cb -0.532909 cr; B +2.112402 cb
+ *     (every sum fits in 27 bits; the result is at most 1 from floor(the double formula + 0.5), clamped)
+ * R, G and B go to bytes dst_channel[0..2] of the output pixel, alpha to the remaining byte when pixel_bytes == 4.  Bytes of a
+ * destination row beyond w * pixel_bytes are not touched.
+ * Host checks (TF2_ERR_ARG with a message, before any device call): desc size, each enum in range, (sub_x, sub_y) one of (1,1),
+ * (2,1), (2,2) unless GRAY, pixel_bytes 3 or 4, dst_channel distinct and in 0..pixel_bytes-1, alpha 0..255, blocks_per_image >= 0,
+ * batch >= 1, non-null pointers, [src_dev, src_dev + src_bytes) and [pixels_dev, pixels_dev + pixels_bytes) disjoint.
+ * Device checks: both record tables are device data (refill them between graph replays), so every block validates its image's
+ * records before it touches a byte and status_dev[b] receives 0 or an OR of TF2_YCC_* bits.  cw in the pitch test is
+ * (w + sub_x - 1) >> (sub_x - 1) whatever w holds.  The extent bits are tested in 64 bits and only when the first three are clear.
+ * An image with a nonzero status is neither read nor written; no access leaves either buffer.  GRAY reads neither chroma offset
+ * nor pitch_c.
+ * One kernel of batch * blocks_per_image blocks of 256 threads (0: the library's default, a function of batch alone), each walking
+ * its image's TF2_YCC_TILE_H x TF2_YCC_TILE_W tiles with a stride: the grid does not depend on the records, so a captured graph
+ * stays valid for new frames of new sizes.  No allocation, no synchronisation, no scratch, no atomics; enqueued on hip_stream. */
+#define TF2_YCC_TILE_W 128
+#define TF2_YCC_TILE_H 16
+typedef struct tf2_ycc_src {        /* one per image, in DEVICE memory, refillable between graph replays; 32 bytes */
+  int64_t off_y, off_cb, off_cr;    /* byte offsets of sample (0,0) of each plane in the source buffer */
+  int32_t pitch_y, pitch_c;         /* bytes between rows of the Y plane / of a chroma plane (of the interleaved one when semi-planar) */
+} tf2_ycc_src;
+enum { TF2_YCC_PLANAR = 0, TF2_YCC_SEMI_CBCR = 1, TF2_YCC_SEMI_CRCB = 2, TF2_YCC_GRAY = 3 };    /* layout */
+enum { TF2_YCC_FANCY = 0, TF2_YCC_REPLICATE = 1 };                                              /* upsample */
+enum { TF2_YCC_JFIF = 0, TF2_YCC_BT601 = 1, TF2_YCC_BT709 = 2 };                                /* matrix */
+typedef struct tf2_ycc_desc {
+  uint32_t size;                    /* sizeof(tf2_ycc_desc) */
+  int32_t layout;                   /* PLANAR (3 planes), SEMI_CBCR (NV12: off_cb -> CbCr pairs, off_cr not read), SEMI_CRCB (NV21:
+                                       off_cb -> CrCb pairs), GRAY (chroma not read, Cb = Cr = 128) */
+  int32_t sub_x, sub_y;             /* (1,1), (2,1) or (2,2); GRAY: ignored */
+  int32_t upsample;                 /* FANCY (libjpeg's triangle filter) or REPLICATE */
+  int32_t matrix;                   /* JFIF (full range, libjpeg's tables), BT601, BT709 (limited range) */
+  int32_t pixel_bytes;              /* 3 or 4 */
+  int32_t dst_channel[3];           /* the byte of an output pixel that receives R, G, B: distinct, in 0..pixel_bytes-1 */
+  int32_t alpha;                    /* 0..255, written to the fourth byte when pixel_bytes == 4 */
+  int32_t blocks_per_image;         /* >= 1; 0: the library's default */
+} tf2_ycc_desc;
+enum {                              /* status_dev bits of an image that was not converted */
+  TF2_YCC_BAD_SIZE = 1,             /* h or w outside 1..32767 */
+  TF2_YCC_BAD_PITCH = 2,            /* row_pitch < w * pixel_bytes, pitch_y < w, pitch_c < cw (2 * cw when semi-planar) */
+  TF2_YCC_BAD_OFFSET = 4,           /* a negative offset that is read (the destination's, off_y, off_cb, PLANAR: off_cr) */
+  TF2_YCC_OUT_OF_SRC = 8,           /* a plane's extent leaves [0, src_bytes) */
+  TF2_YCC_OUT_OF_DST = 16           /* offset + (h-1) * row_pitch + w * pixel_bytes > pixels_bytes */
+};
+tf2_status tf2_ycc_to_rgb(const tf2_ycc_desc* d, const uint8_t* src_dev, size_t src_bytes, const tf2_ycc_src* ycc_dev,
+                          uint8_t* pixels_dev, size_t pixels_bytes, const tf2_image_src* srcs_dev, int batch,
+                          int32_t* status_dev, void* hip_stream);
+
 /* ---- Classification on the device (Evaluation, network_helper.cpp:143-207; INTEGRATION.md "Classification on the device") ----
  * A classifier belongs to a network handle whose final map is 1 x 1 (it reads the handle's q table at create: a later set_q needs
  * a new classifier).  Per image, from the int8 logits [batch][n] a run writes (n = N of the last row) and the runtime Q row of the

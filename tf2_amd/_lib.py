@@ -87,6 +87,18 @@ class RoiDesc(C.Structure):
                 ("square", C.c_int32), ("clip", C.c_int32)]
 
 
+class YccSrc(C.Structure):
+    """tf2_ycc_src (include/tf2_amd.h): the planes of one image, in device memory."""
+    _fields_ = [("off_y", C.c_int64), ("off_cb", C.c_int64), ("off_cr", C.c_int64), ("pitch_y", C.c_int32), ("pitch_c", C.c_int32)]
+
+
+class YccDesc(C.Structure):
+    """tf2_ycc_desc (include/tf2_amd.h)."""
+    _fields_ = [("size", C.c_uint32), ("layout", C.c_int32), ("sub_x", C.c_int32), ("sub_y", C.c_int32), ("upsample", C.c_int32),
+                ("matrix", C.c_int32), ("pixel_bytes", C.c_int32), ("dst_channel", C.c_int32 * 3), ("alpha", C.c_int32),
+                ("blocks_per_image", C.c_int32)]
+
+
 class EmbDesc(C.Structure):
     """tf2_emb_desc (include/tf2_amd.h)."""
     _fields_ = [("size", C.c_uint32), ("top_k", C.c_int32)]
@@ -231,6 +243,7 @@ def lib() -> C.CDLL:
     L.tf2_preprocess_aa.argtypes = L.tf2_preprocess.argtypes
     L.tf2_roi_select.argtypes = [C.POINTER(RoiDesc), vp, vp, vp, C.c_int, vp, vp, vp]
     L.tf2_roi_crop.argtypes = [vp, C.POINTER(PreprocessDesc), vp, sz, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp]
+    L.tf2_ycc_to_rgb.argtypes = [C.POINTER(YccDesc), vp, sz, vp, vp, sz, vp, C.c_int, vp, vp]
     L.tf2_cls_create.argtypes = [vp, C.POINTER(ClsDesc), C.POINTER(vp)]
     L.tf2_cls_destroy.argtypes = [vp]
     L.tf2_cls_destroy.restype = None
@@ -305,7 +318,7 @@ EXPORTED = [
     "tf2_net_packed_adopt", "tf2_net_bind_device", "tf2_net_workspace_size", "tf2_net_logits_size", "tf2_net_reload_options", "tf2_net_run",
     "tf2_net_run_q", "tf2_net_run_ex", "tf2_net_run_stats", "tf2_net_poll_error", "tf2_net_describe_launches", "tf2_net_describe_workspace", "tf2_net_read_layer", "tf2_net_profile", "tf2_net_profile_read", "tf2_net_profile_loop_read", "tf2_topk",
     "tf2_ssd_create", "tf2_ssd_destroy", "tf2_ssd_workspace_size", "tf2_ssd_detect_scratch_size", "tf2_ssd_run", "tf2_ssd_detect",
-    "tf2_preprocess", "tf2_preprocess_aa", "tf2_roi_select", "tf2_roi_crop", "tf2_cls_create", "tf2_cls_destroy", "tf2_cls_run",
+    "tf2_preprocess", "tf2_preprocess_aa", "tf2_roi_select", "tf2_roi_crop", "tf2_ycc_to_rgb", "tf2_cls_create", "tf2_cls_destroy", "tf2_cls_run",
     "tf2_det_eval_create", "tf2_det_eval_destroy", "tf2_det_eval_store_size", "tf2_det_eval_store_init", "tf2_det_eval_run",
     "tf2_det_eval_summarise",
     "tf2_emb_create", "tf2_emb_destroy", "tf2_emb_scratch_size", "tf2_emb_embed", "tf2_emb_match",

@@ -11,6 +11,7 @@
 #include "embed_match.h"
 #include "embed_roc.h"
 #include "roi_crop.h"
+#include "ycc_convert.h"
 #include "act_audit.h"
 #include "act_fidelity.h"
 #include "act_caq.h"
@@ -330,6 +331,11 @@ tf2_status tf2_roi_crop(const tf2_net* net2, const tf2_preprocess_desc* d, const
                         int32_t* status_dev, void* stream) {
   CHECK_NET(net2);
   return roi_crop(net2->impl, d, pixels_dev, pixels_bytes, srcs_dev, batch, rois_dev, n_slots, out_q, out_dev, status_dev, stream);
+}
+
+tf2_status tf2_ycc_to_rgb(const tf2_ycc_desc* d, const uint8_t* src_dev, size_t src_bytes, const tf2_ycc_src* ycc_dev, uint8_t* pixels_dev,
+                          size_t pixels_bytes, const tf2_image_src* srcs_dev, int batch, int32_t* status_dev, void* stream) {
+  return ycc_to_rgb(d, src_dev, src_bytes, ycc_dev, pixels_dev, pixels_bytes, srcs_dev, batch, status_dev, stream);
 }
 
 tf2_status tf2_cls_create(tf2_net* net, const tf2_cls_desc* d, tf2_cls** out) {
