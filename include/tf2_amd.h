@@ -481,6 +481,118 @@ tf2_status tf2_ycc_to_rgb(const tf2_ycc_desc* d, const uint8_t* src_dev, size_t 
                           uint8_t* pixels_dev, size_t pixels_bytes, const tf2_image_src* srcs_dev, int batch,
                           int32_t* status_dev, void* hip_stream);
 
+/* ---- JPEG files on the device (INTEGRATION.md "JPEG files on the device") ----
+ * The step in front of tf2_ycc_to_rgb: a baseline JPEG file -> the planes libjpeg's decoder (and with it Pillow's) reconstructs,
+ * byte for byte, written where the tf2_ycc_src records of tf2_ycc_to_rgb point.  The serial part runs on the host (tf2_jpeg_parse,
+ * tf2_jpeg_entropy: headers and Huffman decoding, csrc/jpeg_entropy.cpp), dequantisation and the inverse DCT on the device
+ * (tf2_jpeg_idct, csrc/jpeg_idct.hip).  tests/golden/pil_jpeg.npz holds Pillow's own bytes; tf2_amd.jpeg.reference is the host
+ * statement of the device call and the device is bit-identical to it.
+ * The arithmetic (libjpeg's "islow" integer inverse DCT, jidctint.c).  A block is 64 int16 coefficients c[v][u], v the vertical and
+ * u the horizontal frequency, in natural (row-major) order, with a quantiser q[v][u] (uint16, natural order).  All sums, products and
+ * left shifts wrap modulo 2^32 (computed unsigned); every >> is arithmetic on the wrapped value.  d[v][u] = c[v][u] * q[v][u].  The
+ * 1-D kernel K(x0..x7; s):
+ *   z1 = (x2+x6)*4433;  t2 = z1 - x6*15137;  t3 = z1 + x2*6270
+ *   t0 = (x0+x4) << 13;  t1 = (x0-x4) << 13
+ *   a0 = t0+t3;  a3 = t0-t3;  a1 = t1+t2;  a2 = t1-t2
+ *   b0 = x7;  b1 = x5;  b2 = x3;  b3 = x1
+ *   z1 = b0+b3;  z2 = b1+b2;  z3 = b0+b2;  z4 = b1+b3;  z5 = (z3+z4)*9633
+ *   b0 *= 2446;  b1 *= 16819;  b2 *= 25172;  b3 *= 12299
+ *   z1 *= -7373;  z2 *= -20995;  z3 = z3*(-16069) + z5;  z4 = z4*(-3196) + z5
+ *   b0 += z1+z3;  b1 += z2+z4;  b2 += z2+z3;  b3 += z1+z4
+ *   out = [a0+b3, a1+b2, a2+b1, a3+b0, a3-b0, a2-b1, a1-b2, a0-b3], each (o + (1 << (s-1))) >> s
+ * Pass 1 runs down each column u: x_k = d[k][u], s = 11, giving ws[k][u].  Pass 2 runs along each row k: x_j = ws[k][j], s = 18.
+ * The sample is clamp(out + 128, 0, 255).  (libjpeg's shortcuts for zero columns and rows give the same values.  For the streams a
+ * conformant encoder writes nothing wraps; the wrap rule makes hostile input defined.)
+ *
+ * tf2_jpeg_parse reads the headers of `file` into *info: the size, the component count (1 or 3), (sub_x, sub_y), the restart
+ * interval, per component the block grid bw x bh of the scan (padded to whole MCUs for three components, ceil(w/8) x ceil(h/8) for
+ * one), the plane size ph x pw (Y: h x w; chroma: ceil(h / sub_y) x ceil(w / sub_x)) and the quantiser in natural order (from 8- or
+ * 16-bit DQT entries), the total block count, and `upsample`, the rule libjpeg applies to this file's chroma: TF2_YCC_REPLICATE when
+ * the file is subsampled and the chroma plane is at most 2 samples wide (jdsample.c filters only wider planes), TF2_YCC_FANCY
+ * otherwise.  Accepted: SOF0, and SOF1 with 8-bit samples; Huffman coding; one scan holding all components; luma sampling 1x1, 2x1
+ * or 2x2 with chroma 1x1, or a single component; DRI / RSTn; any APPn / COM.  Everything else sets TF2_JPEG_UNSUPPORTED_* bits in
+ * info->status (and nothing is decoded, so a caller can fall back): progressive and the other non-sequential Huffman processes,
+ * arithmetic coding, 12-bit samples, a component count other than 1 or 3, other sampling factors, a scan that does not hold every
+ * component, and RGB data by libjpeg's rule (no JFIF marker and an Adobe marker with transform 0, or neither marker and the
+ * component ids 'R', 'G', 'B').  A malformed header sets TF2_JPEG_BAD_HEADER.  The return value is TF2_ERR_ARG for null arguments
+ * and TF2_OK otherwise: what the file is like is in info->status.
+ * tf2_jpeg_entropy decodes the scan of a file whose info->status is 0 into dense blocks of 64 int16 in natural order: component
+ * after component, each in raster order over its bw x bh grid (component c starts at block sum of bw * bh of the components before
+ * it), with DC prediction, EOB and ZRL runs, byte stuffing and restart markers (predictors reset).  Values are stored as int16
+ * with wrap.  Whatever the bytes hold it reads nothing outside [file, file + bytes) and writes nothing outside coef[0 ..
+ * info->total_blocks * 64), which it zeroes first; capacity_blocks < info->total_blocks is TF2_ERR_SIZE and nothing is written.
+ * *status receives 0, TF2_JPEG_TRUNCATED (the stream ends, or a marker stands, where bits or a restart marker are needed) or
+ * TF2_JPEG_BAD_CODE (a code no table holds, a coefficient index beyond 63, a DC category above 15, a wrong restart marker), or
+ * the parser's bits if the headers do not parse to what `info` says; blocks not reached stay zero.  Both calls are host only, touch
+ * no global state and may run on many threads at once; neither sets tf2_last_error.
+ *
+ * tf2_jpeg_idct, image b: its coefficients are described by jpeg_dev[b] (block offsets into coef_dev, in blocks of 64 int16, and
+ * the grids), its quantisers are quant_dev[b][c][64], its sizes h x w come from srcs_dev[b] (nothing else of that record is read)
+ * and its planes go where ycc_dev[b] points in planes_dev: exactly ph x pw samples of each plane and no other byte (the rest of
+ * an edge block is computed and dropped; blocks wholly outside the plane are not read).  d->layout is TF2_YCC_PLANAR (three
+ * components, (sub_x, sub_y) one of (1,1), (2,1), (2,2)) or TF2_YCC_GRAY (one component: component 0 alone is read and off_y,
+ * pitch_y alone of the ycc record).  A batch shares one desc: group files by layout and subsampling.
+ * Host checks (TF2_ERR_ARG with a message, before any device call): desc size, layout PLANAR or GRAY, (sub_x, sub_y) unless GRAY,
+ * blocks_per_image >= 0, batch >= 1, non-null pointers, coef_blocks * 128 representable, the coefficient and the plane buffer
+ * disjoint.
+ * Device checks: all four tables are device data (refill them between graph replays), so every block validates its image's
+ * records before it touches a byte and status_dev[b] receives 0 or an OR of TF2_JPEG_REC_* bits; the extent bits are tested in 64
+ * bits and only when the others are clear.  An image with a nonzero status is neither read nor written.
+ * One kernel of batch * blocks_per_image blocks of 256 threads (0: the library's default, a function of batch alone), each walking
+ * its image's tiles of TF2_JPEG_TILE_BH x TF2_JPEG_TILE_BW coefficient blocks (a tile lies in one plane) with a stride: the grid
+ * does not depend on the records, so a captured graph stays valid for new files of new sizes.  No allocation, no synchronisation,
+ * no scratch, no atomics; enqueued on hip_stream. */
+#define TF2_JPEG_TILE_BW 8
+#define TF2_JPEG_TILE_BH 4
+enum {                              /* tf2_jpeg_info.status and tf2_jpeg_entropy's *status */
+  TF2_JPEG_UNSUPPORTED_PROGRESSIVE = 1,   /* SOF2, and the lossless / hierarchical Huffman processes SOF3, 5, 6, 7 */
+  TF2_JPEG_UNSUPPORTED_ARITHMETIC = 2,    /* SOF9 .. SOF15, or a DAC segment */
+  TF2_JPEG_UNSUPPORTED_PRECISION = 4,     /* samples that are not 8 bits */
+  TF2_JPEG_UNSUPPORTED_COMPONENTS = 8,    /* a component count other than 1 or 3 */
+  TF2_JPEG_UNSUPPORTED_SAMPLING = 16,     /* luma not 1x1, 2x1 or 2x2, or chroma not 1x1 */
+  TF2_JPEG_UNSUPPORTED_SCANS = 32,        /* a scan that does not hold every component */
+  TF2_JPEG_UNSUPPORTED_COLORSPACE = 64,   /* three components that libjpeg takes as RGB */
+  TF2_JPEG_BAD_HEADER = 128,              /* no SOI, a segment that leaves the file, a table or a field out of range, no SOF / SOS */
+  TF2_JPEG_TRUNCATED = 256,               /* entropy decoder: the data ends before the last block */
+  TF2_JPEG_BAD_CODE = 512                 /* entropy decoder: an invalid code, run or restart marker */
+};
+typedef struct tf2_jpeg_info {      /* 480 bytes */
+  int32_t status;                   /* 0, or TF2_JPEG_* bits: the other fields are then not meaningful */
+  int32_t h, w, components;         /* 1..65535; 1 or 3 */
+  int32_t sub_x, sub_y;             /* (1,1), (2,1), (2,2); one component: (1,1) */
+  int32_t restart_interval;         /* MCUs between restart markers, 0: none */
+  int32_t upsample;                 /* TF2_YCC_FANCY or TF2_YCC_REPLICATE: what libjpeg does to this file's chroma */
+  int32_t bw[3], bh[3];             /* the block grid of each component in the scan */
+  int32_t ph[3], pw[3];             /* the plane of each component, in samples */
+  int64_t total_blocks;             /* sum of bw * bh */
+  int64_t scan_offset;              /* byte offset of the entropy-coded data in the file */
+  uint16_t quant[3][64];            /* natural order */
+} tf2_jpeg_info;
+typedef struct tf2_jpeg_src {       /* one per image, in DEVICE memory, refillable between graph replays; 48 bytes */
+  int64_t block_off[3];             /* first block of each component in coef_dev, in blocks of 64 int16 */
+  int32_t bw[3], bh[3];             /* the block grid of each component: block (by, bx) is block_off + by * bw + bx */
+} tf2_jpeg_src;
+typedef struct tf2_jpeg_desc {
+  uint32_t size;                    /* sizeof(tf2_jpeg_desc) */
+  int32_t layout;                   /* TF2_YCC_PLANAR or TF2_YCC_GRAY */
+  int32_t sub_x, sub_y;             /* (1,1), (2,1) or (2,2); GRAY: ignored */
+  int32_t blocks_per_image;         /* >= 1; 0: the library's default */
+} tf2_jpeg_desc;
+enum {                              /* status_dev bits of an image that was not reconstructed */
+  TF2_JPEG_REC_BAD_SIZE = 1,        /* h or w outside 1..32767 */
+  TF2_JPEG_REC_BAD_GRID = 2,        /* a bw or bh below 1, or 8 * bw < pw, or 8 * bh < ph */
+  TF2_JPEG_REC_BAD_PITCH = 4,       /* pitch_y < w, or pitch_c < cw */
+  TF2_JPEG_REC_BAD_OFFSET = 8,      /* a negative offset that is used (block_off[c], off_y, PLANAR: off_cb, off_cr) */
+  TF2_JPEG_REC_OUT_OF_COEF = 16,    /* block_off[c] + bw * bh > coef_blocks */
+  TF2_JPEG_REC_OUT_OF_PLANES = 32   /* a plane's extent leaves [0, planes_bytes) */
+};
+tf2_status tf2_jpeg_parse(const uint8_t* file, size_t bytes, tf2_jpeg_info* info);
+tf2_status tf2_jpeg_entropy(const uint8_t* file, size_t bytes, const tf2_jpeg_info* info, int16_t* coef, size_t capacity_blocks,
+                            int32_t* status);
+tf2_status tf2_jpeg_idct(const tf2_jpeg_desc* d, const int16_t* coef_dev, size_t coef_blocks, const tf2_jpeg_src* jpeg_dev,
+                         const uint16_t* quant_dev, uint8_t* planes_dev, size_t planes_bytes, const tf2_ycc_src* ycc_dev,
+                         const tf2_image_src* srcs_dev, int batch, int32_t* status_dev, void* hip_stream);
+
 /* ---- Classification on the device (Evaluation, network_helper.cpp:143-207; INTEGRATION.md "Classification on the device") ----
  * A classifier belongs to a network handle whose final map is 1 x 1 (it reads the handle's q table at create: a later set_q needs
  * a new classifier).  Per image, from the int8 logits [batch][n] a run writes (n = N of the last row) and the runtime Q row of the

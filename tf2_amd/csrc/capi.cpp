@@ -12,6 +12,7 @@
 #include "embed_roc.h"
 #include "roi_crop.h"
 #include "ycc_convert.h"
+#include "jpeg_idct.h"
 #include "act_audit.h"
 #include "act_fidelity.h"
 #include "act_caq.h"
@@ -336,6 +337,13 @@ tf2_status tf2_roi_crop(const tf2_net* net2, const tf2_preprocess_desc* d, const
 tf2_status tf2_ycc_to_rgb(const tf2_ycc_desc* d, const uint8_t* src_dev, size_t src_bytes, const tf2_ycc_src* ycc_dev, uint8_t* pixels_dev,
                           size_t pixels_bytes, const tf2_image_src* srcs_dev, int batch, int32_t* status_dev, void* stream) {
   return ycc_to_rgb(d, src_dev, src_bytes, ycc_dev, pixels_dev, pixels_bytes, srcs_dev, batch, status_dev, stream);
+}
+
+// (tf2_jpeg_parse and tf2_jpeg_entropy are defined in jpeg_entropy.cpp, which builds without the rest of the library)
+tf2_status tf2_jpeg_idct(const tf2_jpeg_desc* d, const int16_t* coef_dev, size_t coef_blocks, const tf2_jpeg_src* jpeg_dev,
+                         const uint16_t* quant_dev, uint8_t* planes_dev, size_t planes_bytes, const tf2_ycc_src* ycc_dev,
+                         const tf2_image_src* srcs_dev, int batch, int32_t* status_dev, void* stream) {
+  return jpeg_idct(d, coef_dev, coef_blocks, jpeg_dev, quant_dev, planes_dev, planes_bytes, ycc_dev, srcs_dev, batch, status_dev, stream);
 }
 
 tf2_status tf2_cls_create(tf2_net* net, const tf2_cls_desc* d, tf2_cls** out) {
