@@ -593,6 +593,94 @@ tf2_status tf2_jpeg_idct(const tf2_jpeg_desc* d, const int16_t* coef_dev, size_t
                          const uint16_t* quant_dev, uint8_t* planes_dev, size_t planes_bytes, const tf2_ycc_src* ycc_dev,
                          const tf2_image_src* srcs_dev, int batch, int32_t* status_dev, void* hip_stream);
 
+/* ---- JPEG entropy decoding on the device (INTEGRATION.md "JPEG entropy decoding on the device") ----
+ * The step in front of tf2_jpeg_idct, as an alternative to tf2_jpeg_entropy: the entropy-coded bytes of a batch of files ->
+ * the dense blocks of 64 int16 coefficients tf2_jpeg_idct reads (tf2_jpeg_huff, csrc/jpeg_huff.hip).  The host only parses the
+ * headers (tf2_jpeg_parse) and copies the Huffman tables into a record (tf2_jpeg_scan_fill).  tf2_amd.jpeg.reference_huff is the
+ * host statement of the device call -- the same parallel algorithm, not a serial decoder -- and the device is bit-identical to it.
+ *
+ * Records.  Image b's entropy-coded data is bytes_dev[scan_dev[b].byte_off .. + byte_len): from info.scan_offset to the end of
+ * the file, trailing bytes included.  scan_dev[b] also holds the component count, (sub_x, sub_y), the restart interval and per
+ * component the raw canonical tables of its DC and AC code (counts of the codes of length 1..16, symbols in code order); the device
+ * builds its lookup tables in LDS.  The block grids and where the blocks go come from jpeg_dev[b], the tf2_jpeg_src record that
+ * tf2_jpeg_idct reads.  tf2_jpeg_scan_fill fills a record from a file and the info tf2_jpeg_parse made of it (host only, no state,
+ * thread safe, sets no tf2_last_error; TF2_ERR_ARG for null arguments, an info whose status is not 0, or headers that no longer
+ * parse to what info says).
+ *
+ * The algorithm (self-synchronising Huffman decoding: Klein and Wiseman; Weissenberger and Schmidt for JPEG).  The data is cut into
+ * N = max(1, ceil(byte_len / subseq_bytes)) subsequences, one lane each.  A decoder state is the bit reader's position (with, for
+ * files with a restart interval, the count of whole bytes the host's 64-bit accumulator holds ahead of it, which tf2_jpeg_entropy's
+ * restart rule depends on), the block's index inside the MCU, and the zigzag index k (0: a DC code is due).  A step is one code
+ * with its extra bits; it belongs to the subsequence its first bit lies in, and a lane decodes steps from its entry state until the
+ * position leaves its subsequence (the last lane: until the data ends) and records the exit state, the blocks it completed and the
+ * sum of the DC differences per component, both since the last restart marker it passed, and the markers passed.
+ *   Round 0: every lane starts at its first bit (behind the 00 of a stuffed pair that straddles the boundary) with block 0, k 0.
+ *   Round r: a lane whose entry (its left neighbour's exit of round r - 1) changed decodes again; others keep their exit.
+ *   When no entry changes the chain of states is the serial decoder's.  After round r the first r + 1 lanes are certainly right,
+ *   so N rounds is the worst case -- a serial decode.  Lanes are processed in chunks of min(TF2_JPEG_HUFF_LANES, 65536 /
+ *   subseq_bytes, 16 * subseq_bytes) -- 256, 512, 1024, 512, 256 for 16 .. 256 bytes; a chunk's converged exit is the next chunk's
+ *   first entry.
+ * The rounds decode TOLERANTLY, or wrongly started lanes never meet the right chain: a code no table holds skips one bit, a DC
+ * category above 15 is 15, a zigzag index beyond 63 ends the block, and where the valid bits end (a marker, FF followed by anything
+ * but 00, or the end of the data) in front of an RSTn the lane steps over the marker to (block 0, k 0) with an empty reader; any
+ * other marker or the end is a terminal "stopped" state.  Every step consumes at least one bit, a marker, or stops.
+ * Errors are judged afterwards, in a STRICT pass over the converged chain with tf2_jpeg_entropy's own rules: a prefix sum over the
+ * lanes' counts gives every lane the scan-order index of its first block, the restart markers passed and the DC predictors, and
+ * the lane decodes once more, writing DC values and nonzero AC coefficients in natural order at the host decoder's block index
+ * (the extent was zeroed first).  Bits that run out are TF2_JPEG_TRUNCATED; a code no table holds (with 16 bits to look at), a DC
+ * category above 15, an index beyond 63, and a restart marker that does not stand at the host reader's fill pointer with the right
+ * number where an interval ends are TF2_JPEG_BAD_CODE.  Decoding stops at the image's total block count; trailing bytes are
+ * ignored.  The first error in chain order is the status.
+ *
+ * Contract.  For a file tf2_jpeg_entropy decodes with status 0 the image's coefficient extent equals the host decoder's buffer bit
+ * for bit and status_dev[b] is 0, for every subseq_bytes.  For a file it decodes with TF2_JPEG_TRUNCATED or TF2_JPEG_BAD_CODE,
+ * status_dev[b] is one of those two (which of them may differ from the host's, whose bit reader looks further ahead) and -- a
+ * stated difference from the host, which leaves the blocks before the error -- the image's whole extent is zero.
+ * Device checks: every workgroup validates its image's records before it touches a byte; an image with a TF2_JPEG_REC_* bit is
+ * neither read nor written (status_dev[b] alone), other images are unaffected.  Nothing is read outside the image's byte range
+ * and nothing written outside its coefficient extent, its slice of the workspace and status_dev[b], whatever the bytes hold.
+ * Termination: rounds are at most the lanes of a chunk, chunks ceil(N / lanes of a chunk), a lane's steps at most 9 * byte_len
+ * + 64; no workgroup waits for another, nothing is polled.
+ * Workspace: image b's slice is work_dev[b * (work_bytes / batch rounded down to 8) ...]: int32 {rounds used, N, 0, 0}
+ * then 8 bytes per subsequence (its converged exit state).  tf2_jpeg_huff_work_bytes(d, batch, max_scan_bytes) is the size that
+ * takes byte_len up to max_scan_bytes.
+ * Host checks (TF2_ERR_ARG with a "tf2_jpeg_huff:" message, before any device call): desc size, layout PLANAR or GRAY, (sub_x,
+ * sub_y) unless GRAY, subseq_bytes 0, 16, 32, 64, 128 or 256, batch >= 1, non-null pointers, coef_dev 16-byte and work_dev 8-byte
+ * aligned, coef_blocks * 128 representable, work_bytes >= tf2_jpeg_huff_work_bytes(d, batch, 0), and the byte, coefficient,
+ * workspace and status buffers pairwise disjoint.
+ * One kernel of `batch` workgroups of TF2_JPEG_HUFF_LANES threads, whatever the records hold: a captured graph stays valid for new
+ * files of new sizes.  No allocation, no synchronisation, no host copy, no scratch; enqueued on hip_stream. */
+#define TF2_JPEG_HUFF_LANES 1024
+#define TF2_JPEG_HUFF_DEFAULT_SUBSEQ 64
+#define TF2_JPEG_HUFF_MAX_BYTES (1 << 28)
+typedef struct tf2_jpeg_scan {      /* one per image, in DEVICE memory, refillable between graph replays; 1664 bytes */
+  int64_t byte_off, byte_len;       /* the entropy-coded data in bytes_dev; byte_len <= TF2_JPEG_HUFF_MAX_BYTES */
+  int32_t components;               /* 1 or 3: must agree with the desc */
+  int32_t sub_x, sub_y;             /* must agree with the desc (one component: 1, 1) */
+  int32_t restart_interval;         /* 0..65535 */
+  struct {
+    uint8_t dc_counts[16], dc_vals[256];   /* codes of length 1..16; the symbols in code order */
+    uint8_t ac_counts[16], ac_vals[256];
+  } tab[3];                         /* per component */
+} tf2_jpeg_scan;
+typedef struct tf2_jpeg_huff_desc {
+  uint32_t size;                    /* sizeof(tf2_jpeg_huff_desc) */
+  int32_t layout;                   /* TF2_YCC_PLANAR or TF2_YCC_GRAY */
+  int32_t sub_x, sub_y;             /* (1,1), (2,1) or (2,2); GRAY: ignored */
+  int32_t subseq_bytes;             /* 16, 32, 64, 128 or 256; 0: TF2_JPEG_HUFF_DEFAULT_SUBSEQ */
+} tf2_jpeg_huff_desc;
+enum {                              /* further status_dev bits of tf2_jpeg_huff (with REC_BAD_GRID, REC_BAD_OFFSET, REC_OUT_OF_COEF) */
+  TF2_JPEG_REC_BAD_RANGE = 1024,    /* byte_off or byte_len negative, byte_len too large, or the range leaves [0, bytes_len) */
+  TF2_JPEG_REC_BAD_SCAN = 2048,     /* components, sub_x, sub_y disagree with the desc, or restart_interval outside 0..65535 */
+  TF2_JPEG_REC_BAD_TABLE = 4096,    /* counts that are no canonical code: more than 256 symbols or a code that does not fit its length */
+  TF2_JPEG_REC_WORK_TOO_SMALL = 8192 /* the image's workspace slice is smaller than 16 + 8 * N */
+};
+tf2_status tf2_jpeg_scan_fill(const uint8_t* file, size_t bytes, const tf2_jpeg_info* info, int64_t byte_off, tf2_jpeg_scan* out);
+size_t tf2_jpeg_huff_work_bytes(const tf2_jpeg_huff_desc* d, int batch, size_t max_scan_bytes);
+tf2_status tf2_jpeg_huff(const tf2_jpeg_huff_desc* d, const uint8_t* bytes_dev, size_t bytes_len, const tf2_jpeg_scan* scan_dev,
+                         const tf2_jpeg_src* jpeg_dev, int16_t* coef_dev, size_t coef_blocks, uint8_t* work_dev, size_t work_bytes,
+                         int batch, int32_t* status_dev, void* hip_stream);
+
 /* ---- Classification on the device (Evaluation, network_helper.cpp:143-207; INTEGRATION.md "Classification on the device") ----
  * A classifier belongs to a network handle whose final map is 1 x 1 (it reads the handle's q table at create: a later set_q needs
  * a new classifier).  Per image, from the int8 logits [batch][n] a run writes (n = N of the last row) and the runtime Q row of the

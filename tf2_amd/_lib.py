@@ -112,6 +112,21 @@ class JpegSrc(C.Structure):
     _fields_ = [("block_off", C.c_int64 * 3), ("bw", C.c_int32 * 3), ("bh", C.c_int32 * 3)]
 
 
+class JpegScanTab(C.Structure):
+    _fields_ = [("dc_counts", C.c_uint8 * 16), ("dc_vals", C.c_uint8 * 256), ("ac_counts", C.c_uint8 * 16), ("ac_vals", C.c_uint8 * 256)]
+
+
+class JpegScan(C.Structure):
+    """tf2_jpeg_scan (include/tf2_amd.h): where a file's entropy-coded bytes lie and its Huffman tables, in device memory."""
+    _fields_ = [("byte_off", C.c_int64), ("byte_len", C.c_int64), ("components", C.c_int32), ("sub_x", C.c_int32), ("sub_y", C.c_int32),
+                ("restart_interval", C.c_int32), ("tab", JpegScanTab * 3)]
+
+
+class JpegHuffDesc(C.Structure):
+    """tf2_jpeg_huff_desc (include/tf2_amd.h)."""
+    _fields_ = [("size", C.c_uint32), ("layout", C.c_int32), ("sub_x", C.c_int32), ("sub_y", C.c_int32), ("subseq_bytes", C.c_int32)]
+
+
 class JpegDesc(C.Structure):
     """tf2_jpeg_desc (include/tf2_amd.h)."""
     _fields_ = [("size", C.c_uint32), ("layout", C.c_int32), ("sub_x", C.c_int32), ("sub_y", C.c_int32), ("blocks_per_image", C.c_int32)]
@@ -265,6 +280,10 @@ def lib() -> C.CDLL:
     L.tf2_jpeg_parse.argtypes = [vp, sz, C.POINTER(JpegInfo)]
     L.tf2_jpeg_entropy.argtypes = [vp, sz, C.POINTER(JpegInfo), vp, sz, i32p]
     L.tf2_jpeg_idct.argtypes = [C.POINTER(JpegDesc), vp, sz, vp, vp, vp, sz, vp, vp, C.c_int, vp, vp]
+    L.tf2_jpeg_scan_fill.argtypes = [vp, sz, C.POINTER(JpegInfo), C.c_int64, C.POINTER(JpegScan)]
+    L.tf2_jpeg_huff_work_bytes.argtypes = [C.POINTER(JpegHuffDesc), C.c_int, sz]
+    L.tf2_jpeg_huff_work_bytes.restype = sz
+    L.tf2_jpeg_huff.argtypes = [C.POINTER(JpegHuffDesc), vp, sz, vp, vp, vp, sz, vp, sz, C.c_int, vp, vp]
     L.tf2_cls_create.argtypes = [vp, C.POINTER(ClsDesc), C.POINTER(vp)]
     L.tf2_cls_destroy.argtypes = [vp]
     L.tf2_cls_destroy.restype = None
@@ -339,7 +358,7 @@ EXPORTED = [
     "tf2_net_packed_adopt", "tf2_net_bind_device", "tf2_net_workspace_size", "tf2_net_logits_size", "tf2_net_reload_options", "tf2_net_run",
     "tf2_net_run_q", "tf2_net_run_ex", "tf2_net_run_stats", "tf2_net_poll_error", "tf2_net_describe_launches", "tf2_net_describe_workspace", "tf2_net_read_layer", "tf2_net_profile", "tf2_net_profile_read", "tf2_net_profile_loop_read", "tf2_topk",
     "tf2_ssd_create", "tf2_ssd_destroy", "tf2_ssd_workspace_size", "tf2_ssd_detect_scratch_size", "tf2_ssd_run", "tf2_ssd_detect",
-    "tf2_preprocess", "tf2_preprocess_aa", "tf2_roi_select", "tf2_roi_crop", "tf2_ycc_to_rgb", "tf2_jpeg_parse", "tf2_jpeg_entropy", "tf2_jpeg_idct", "tf2_cls_create", "tf2_cls_destroy", "tf2_cls_run",
+    "tf2_preprocess", "tf2_preprocess_aa", "tf2_roi_select", "tf2_roi_crop", "tf2_ycc_to_rgb", "tf2_jpeg_parse", "tf2_jpeg_entropy", "tf2_jpeg_idct", "tf2_jpeg_scan_fill", "tf2_jpeg_huff_work_bytes", "tf2_jpeg_huff", "tf2_cls_create", "tf2_cls_destroy", "tf2_cls_run",
     "tf2_det_eval_create", "tf2_det_eval_destroy", "tf2_det_eval_store_size", "tf2_det_eval_store_init", "tf2_det_eval_run",
     "tf2_det_eval_summarise",
     "tf2_emb_create", "tf2_emb_destroy", "tf2_emb_scratch_size", "tf2_emb_embed", "tf2_emb_match",

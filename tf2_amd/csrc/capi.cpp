@@ -13,6 +13,7 @@
 #include "roi_crop.h"
 #include "ycc_convert.h"
 #include "jpeg_idct.h"
+#include "jpeg_huff.h"
 #include "act_audit.h"
 #include "act_fidelity.h"
 #include "act_caq.h"
@@ -344,6 +345,17 @@ tf2_status tf2_jpeg_idct(const tf2_jpeg_desc* d, const int16_t* coef_dev, size_t
                          const uint16_t* quant_dev, uint8_t* planes_dev, size_t planes_bytes, const tf2_ycc_src* ycc_dev,
                          const tf2_image_src* srcs_dev, int batch, int32_t* status_dev, void* stream) {
   return jpeg_idct(d, coef_dev, coef_blocks, jpeg_dev, quant_dev, planes_dev, planes_bytes, ycc_dev, srcs_dev, batch, status_dev, stream);
+}
+
+// (tf2_jpeg_scan_fill is defined in jpeg_entropy.cpp too)
+size_t tf2_jpeg_huff_work_bytes(const tf2_jpeg_huff_desc* d, int batch, size_t max_scan_bytes) {
+  return jpeg_huff_work_bytes(d, batch, max_scan_bytes);
+}
+
+tf2_status tf2_jpeg_huff(const tf2_jpeg_huff_desc* d, const uint8_t* bytes_dev, size_t bytes_len, const tf2_jpeg_scan* scan_dev,
+                         const tf2_jpeg_src* jpeg_dev, int16_t* coef_dev, size_t coef_blocks, uint8_t* work_dev, size_t work_bytes,
+                         int batch, int32_t* status_dev, void* stream) {
+  return jpeg_huff(d, bytes_dev, bytes_len, scan_dev, jpeg_dev, coef_dev, coef_blocks, work_dev, work_bytes, batch, status_dev, stream);
 }
 
 tf2_status tf2_cls_create(tf2_net* net, const tf2_cls_desc* d, tf2_cls** out) {

@@ -1,4 +1,4 @@
-// jpeg_entropy.cpp -- the serial part of a baseline JPEG decoder, on the host (tf2_jpeg_parse, tf2_jpeg_entropy, include/tf2_amd.h):
+// jpeg_entropy.cpp -- the serial part of a baseline JPEG decoder, on the host (tf2_jpeg_parse, tf2_jpeg_entropy, tf2_jpeg_scan_fill, include/tf2_amd.h):
 // the headers, and the Huffman-coded scan into dense blocks of 64 int16 coefficients in natural order that tf2_jpeg_idct
 // (jpeg_idct.hip) dequantises and transforms on the device.  Host only: no device call, no global state, no tf2_last_error -- both
 // entry points may run on many threads at once.  The file needs nothing but the public header, so that it also builds alone
@@ -22,6 +22,7 @@ const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18,
 
 struct Huff {
   bool defined = false;
+  uint8_t counts[16];               // as the DHT segment gives them (tf2_jpeg_scan_fill copies them out)
   uint8_t vals[256];
   int32_t maxcode[17];              // the largest code of length l, -1: none
   int32_t valptr[17], mincode[17];
@@ -53,7 +54,9 @@ bool build_huff(Huff& t, const uint8_t* counts, const uint8_t* vals, int n) {
     t.maxcode[l] = counts[l - 1] ? code - 1 : -1;
     code <<= 1;
   }
+  std::memset(t.vals, 0, sizeof t.vals);
   std::memcpy(t.vals, vals, (size_t)n);
+  std::memcpy(t.counts, counts, 16);
   t.defined = true;
   return k == n;
 }
@@ -345,6 +348,32 @@ tf2_status tf2_jpeg_entropy(const uint8_t* file, size_t bytes, const tf2_jpeg_in
     }
   }
   *status = st;
+  return TF2_OK;
+}
+
+tf2_status tf2_jpeg_scan_fill(const uint8_t* file, size_t bytes, const tf2_jpeg_info* info, int64_t byte_off, tf2_jpeg_scan* out) {
+  if (!file || !info || !out) return TF2_ERR_ARG;
+  if (info->status != 0 || info->total_blocks < 1) return TF2_ERR_ARG;
+  Header H;
+  parse_headers(file, bytes, H);
+  const tf2_jpeg_info& I = H.info;
+  bool same = I.status == 0 && I.h == info->h && I.w == info->w && I.components == info->components &&
+              I.total_blocks == info->total_blocks && I.scan_offset == info->scan_offset;
+  if (!same || I.scan_offset < 0 || (uint64_t)I.scan_offset > bytes) return TF2_ERR_ARG;
+  std::memset(out, 0, sizeof *out);
+  out->byte_off = byte_off;
+  out->byte_len = (int64_t)(bytes - (size_t)I.scan_offset);
+  out->components = I.components;
+  out->sub_x = I.sub_x;
+  out->sub_y = I.sub_y;
+  out->restart_interval = I.restart_interval;
+  for (int c = 0; c < I.components; c++) {
+    const Huff &dc = H.dc[H.comp[c].td], &ac = H.ac[H.comp[c].ta];
+    std::memcpy(out->tab[c].dc_counts, dc.counts, 16);
+    std::memcpy(out->tab[c].dc_vals, dc.vals, 256);
+    std::memcpy(out->tab[c].ac_counts, ac.counts, 16);
+    std::memcpy(out->tab[c].ac_vals, ac.vals, 256);
+  }
   return TF2_OK;
 }
 

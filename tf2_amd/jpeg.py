@@ -12,7 +12,11 @@ Pillow's `Image.open(file).convert("RGB")` byte for byte: tests/golden/pil_jpeg.
 (tools/gen_jpeg_golden.py).
 
 `parse` / `entropy` / `decode_host` are the host step, `pack` builds the device inputs (or refills buffers a captured graph
-reads), `DeviceDecoder(desc).run(...)` is the device call.  A batch shares one desc: group files by `group_key`."""
+reads), `DeviceDecoder(desc).run(...)` is the device call.  A batch shares one desc: group files by `group_key`.
+
+The entropy decoding can run on the device as well (tf2_jpeg_huff, csrc/jpeg_huff.hip; the section at the end of this file):
+`scan_record` is the host fill call, `pack_bytes` builds the device inputs from files' bytes, `DeviceEntropy(desc).run(...)` is the
+device call and `reference_huff` the statement of its parallel algorithm -- subsequences, tolerant rounds, strict pass."""
 import ctypes as C
 from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
@@ -544,3 +548,547 @@ class DeviceDecoder:
         yr = np.ascontiguousarray(host(ycc), np.int32).view(Y.YCC_DTYPE).reshape(-1)
         sr = np.ascontiguousarray(host(srcs), np.int32).view(P.SRC_DTYPE).reshape(-1)
         return reference(host(coef), jr, host(quant).view(np.uint16), yr, sr, self.desc, host(planes))
+
+
+# ---------------------------------------------------------------- entropy decoding on the device (tf2_jpeg_huff, csrc/jpeg_huff.hip)
+
+# tf2_jpeg_scan, byte for byte (1664 bytes)
+SCAN_DTYPE = np.dtype([("byte_off", "<i8"), ("byte_len", "<i8"), ("components", "<i4"), ("sub_x", "<i4"), ("sub_y", "<i4"),
+                       ("restart_interval", "<i4"),
+                       ("tab", [("dc_counts", "u1", (16,)), ("dc_vals", "u1", (256,)), ("ac_counts", "u1", (16,)), ("ac_vals", "u1", (256,))], (3,))])
+SCAN_WORDS = SCAN_DTYPE.itemsize // 4
+HUFF_LANES = 1024                                                # TF2_JPEG_HUFF_LANES: threads of a workgroup
+HUFF_DEFAULT_SUBSEQ = 64
+HUFF_MAX_BYTES = 1 << 28
+HUFF_WORK_HEADER = 16
+REC_BAD_RANGE, REC_BAD_SCAN, REC_BAD_TABLE, REC_WORK_TOO_SMALL = 1024, 2048, 4096, 8192
+_STOPPED = 1 << 16
+_M64 = (1 << 64) - 1
+
+
+@dataclass(frozen=True)
+class HuffDesc:
+    """tf2_jpeg_huff_desc: layout (ycc.PLANAR: three components, ycc.GRAY: one), (sub_x, sub_y), subseq_bytes (0: the default)"""
+    layout: int = Y.PLANAR
+    sub: Tuple[int, int] = (2, 2)
+    subseq_bytes: int = 0
+
+    def c(self):
+        from . import _lib
+        d = _lib.JpegHuffDesc()
+        d.size = C.sizeof(_lib.JpegHuffDesc)
+        d.layout, d.sub_x, d.sub_y, d.subseq_bytes = self.layout, self.sub[0], self.sub[1], self.subseq_bytes
+        return d
+
+    @property
+    def eff_sub(self) -> Tuple[int, int]:
+        return (1, 1) if self.layout == Y.GRAY else tuple(self.sub)
+
+    @property
+    def components(self) -> int:
+        return 1 if self.layout == Y.GRAY else 3
+
+    @property
+    def subseq(self) -> int:
+        return self.subseq_bytes or HUFF_DEFAULT_SUBSEQ
+
+
+def huff_chunk_lanes(subseq_bytes: int) -> int:
+    """subsequences of a chunk (csrc/jpeg_huff.h): 256, 512, 1024, 512, 256 for 16 .. 256 bytes a subsequence"""
+    return min(HUFF_LANES, 65536 // subseq_bytes, 16 * subseq_bytes)
+
+
+def huff_work_bytes(desc: HuffDesc, batch: int, max_scan_bytes: int) -> int:
+    """tf2_jpeg_huff_work_bytes: 16 + 8 bytes a subsequence, per image"""
+    return int(batch) * (HUFF_WORK_HEADER + 8 * max(1, -(-int(max_scan_bytes) // desc.subseq)))
+
+
+def scan_record(data, info: Info, byte_off: int) -> np.ndarray:
+    """tf2_jpeg_scan_fill: the SCAN_DTYPE record (shape ()) of a file whose entropy-coded bytes, data[info.scan_offset:], lie at
+    byte_off of the batch's byte buffer"""
+    from . import _lib
+    assert info.raw is not None, "an Info of `parse` is needed"
+    buf = _bytes(data)
+    raw = _lib.JpegScan()
+    rc = _lib.lib().tf2_jpeg_scan_fill(buf.ctypes.data, buf.size, C.byref(info.raw), int(byte_off), C.byref(raw))
+    if rc != 0:
+        raise _lib.Tf2Error(rc, "tf2_jpeg_scan_fill: null argument, an info whose status is not 0, or headers that do not parse to it")
+    return np.frombuffer(bytes(raw), SCAN_DTYPE)[0].copy()
+
+
+def _huff_table(counts, vals):
+    """(look [512], maxcode [17], valoff [17], vals [256]) of a canonical code, or None: build_huff's test"""
+    counts = [int(v) for v in counts]
+    if sum(counts) > 256:
+        return None
+    vals = [int(v) for v in vals]
+    look, maxcode, valoff, code, k = [0] * 512, [-1] * 17, [0] * 17, 0, 0
+    for ln in range(1, 17):
+        valoff[ln] = k - code
+        for _ in range(counts[ln - 1]):
+            if code >= (1 << ln):
+                return None
+            if ln <= 9:
+                first = code << (9 - ln)
+                look[first:first + (1 << (9 - ln))] = [(ln << 8) | vals[k]] * (1 << (9 - ln))
+            k, code = k + 1, code + 1
+        maxcode[ln] = code - 1 if counts[ln - 1] else -1
+        code <<= 1
+    return look, maxcode, valoff, vals
+
+
+class _HuffImage:
+    """what a lane needs of its image (csrc/jpeg_huff.hip's Ctx)"""
+
+
+def _huff_lane(c, in0, in1, endkey, last, strict, s, tolerant=True):
+    """csrc/jpeg_huff.hip's lane(), statement for statement: (out0, out1, (m, bs, a0 .. a5), err) -- a: the DC sums per block slot
+    from the entry's first block on (rounds) or per component (strict pass).  tolerant False (rounds only): a lane stops at the
+    first impossible event -- the rule that does not synchronise."""
+    if not strict:
+        s = (0, 0, 0, 0, 0, 0, 0, 0)
+    if in1 & _STOPPED:
+        return in0, in1, s, 0
+    d, n = c.d, c.len
+    track = c.ri != 0
+    # -- the reader (p, acc, have, stop, ff) and its entry
+    rem, lead = in1 & 7, (in1 >> 3) & 15
+    p = in0
+    if rem and p >= 1:
+        p = p - 2 if (p >= 2 and d[p - 1] == 0 and d[p - 2] == 0xFF) else p - 1
+    R = [p, 0, 0, False, 0]                                       # p, acc, have, stop, ff
+
+    def load1():
+        q = R[0]
+        if q >= n:
+            R[3] = True
+            return
+        v = d[q]
+        if v == 0xFF:
+            if n - q < 2 or d[q + 1] != 0:
+                R[3] = True
+                return
+            R[0], R[4] = q + 2, ((R[4] << 1) | 1) & 0xFFFFFFFF
+        else:
+            R[0], R[4] = q + 1, (R[4] << 1) & 0xFFFFFFFF
+        R[1] |= v << (56 - R[2])
+        R[2] += 8
+
+    def fill():
+        while R[2] <= 56 and not R[3]:
+            load1()
+
+    def take(k):
+        if k > R[2]:
+            return False
+        R[1] = (R[1] << k) & _M64
+        R[2] -= k
+        return True
+
+    def reset():
+        R[1], R[2], R[3], R[4] = 0, 0, False, 0
+
+    def position():
+        whole, rm = R[2] >> 3, R[2] & 7
+        return R[0] - whole - bin(R[4] & ((1 << whole) - 1)).count("1"), rm, (whole if track else 0)
+
+    def symbol(t):
+        look, maxcode, valoff, vals = t
+        if R[2] < 16:
+            fill()
+        e = look[R[1] >> 55]
+        if e:
+            return (e & 0xFF) if take(e >> 8) else -1
+        for ln in range(10, 17):
+            code = R[1] >> (64 - ln)
+            if code <= maxcode[ln]:
+                if not take(ln):
+                    return -1
+                return vals[(valoff[ln] + code) & 255]
+        return -2
+
+    def extend(sz):
+        if R[2] < sz:
+            fill()
+        r = R[1] >> (64 - sz)
+        if not take(sz):
+            return None
+        return r - (1 << sz) + 1 if r < (1 << (sz - 1)) else r
+
+    for _ in range(lead + (1 if rem else 0)):
+        if R[3]:
+            break
+        load1()
+    if rem and R[2] >= 8:
+        take(8 - rem)
+    blk, k, slot = (in1 >> 7) & 7, (in1 >> 10) & 63, 0
+    freeze = c.same and not strict
+    m, bs = s[0], s[1]
+    dd = list(s[2:])
+    if strict:
+        blk = bs % c.mcub
+    tol, stopped, err, cur = not strict, False, 0, None
+    if strict:
+        g = m * c.rim + bs
+        if g >= c.total:
+            return in0, in1, s, 0
+        if track and (bs > c.rim or (bs == c.rim and k != 0)):
+            tol = True
+        else:
+            cur = c.coef[c.block_of(g)]
+    it = 0
+    while it < c.cap:
+        it += 1
+        pc, rm, ld = position()
+        if not last and pc - (1 if rm else 0) >= endkey:
+            break
+        if not tol and k == 0:
+            g = m * c.rim + bs
+            if g >= c.total:
+                break
+            if track and bs == c.rim:
+                q = R[0]
+                if q >= n:
+                    err = TRUNCATED
+                    break
+                if d[q] != 0xFF:
+                    err = BAD_CODE
+                    break
+                while q < n and d[q] == 0xFF:
+                    q += 1
+                if q >= n:
+                    err = TRUNCATED
+                    break
+                if d[q] != 0xD0 + (m & 7):
+                    err = BAD_CODE
+                    break
+                R[0] = q + 1
+                reset()
+                m, bs, dd, blk = m + 1, 0, [0] * 6, 0
+                continue
+            cur = c.coef[c.block_of(g)]
+        comp = 0 if blk < c.ylum else blk - c.ylum + 1
+        nobits = endblock = False
+        sym = symbol(c.tabs[2 * comp + (1 if k else 0)])
+        if sym == -1:
+            nobits = True
+        elif sym == -2:
+            if not tol:
+                err = TRUNCATED if R[2] < 16 else BAD_CODE
+                break
+            if not tolerant:
+                stopped = True
+                break
+            if not take(1):
+                nobits = True
+        elif k == 0:
+            sz = sym
+            if sz > 15:
+                if not tol:
+                    err = BAD_CODE
+                    break
+                if not tolerant:
+                    stopped = True
+                    break
+                sz = 15
+            v = extend(sz) if sz else 0
+            if v is None:
+                nobits = True
+            else:
+                dd[comp if strict else slot] = (dd[comp if strict else slot] + v) & 0xFFFFFFFF
+                if not tol:
+                    cur[0] = dd[comp] & 0xFFFF
+                k = 1
+        else:
+            r, sz = sym >> 4, sym & 15
+            if sz == 0:
+                if r == 15:
+                    k += 16
+                    if k > 64 and not tol:
+                        err = BAD_CODE
+                        break
+                    if k > 64 and not tolerant:
+                        stopped = True
+                        break
+                    if k >= 64:
+                        endblock = True
+                else:
+                    endblock = True
+            else:
+                k += r
+                if k > 63:
+                    if not tol:
+                        err = BAD_CODE
+                        break
+                    if not tolerant:
+                        stopped = True
+                        break
+                    endblock = True
+                else:
+                    v = extend(sz)
+                    if v is None:
+                        nobits = True
+                    else:
+                        if not tol:
+                            cur[ZIGZAG[k]] = v & 0xFFFF
+                        k += 1
+                        if k >= 64:
+                            endblock = True
+        if nobits:
+            if not tol:
+                err = TRUNCATED
+                break
+            q = R[0]
+            while q < n and d[q] == 0xFF:
+                q += 1
+            if q > R[0] and q < n and (d[q] & 0xF8) == 0xD0:
+                R[0] = q + 1
+                reset()
+                m, bs, dd, blk, k, slot = m + 1, 0, [0] * 6, 0, 0, 0
+                if strict:
+                    tol = False
+                continue
+            stopped = True
+            break
+        if endblock:
+            k, blk, bs = 0, (0 if freeze or blk + 1 == c.mcub else blk + 1), bs + 1
+            slot = 0 if slot + 1 == c.mcub else slot + 1
+    if strict:
+        return in0, in1, s, err
+    pc, rm, ld = position()
+    return pc, rm | ld << 3 | blk << 7 | k << 10 | (_STOPPED if stopped else 0), (m, bs) + tuple(dd), 0
+
+
+def huff_record_status(scan, jrec, desc: HuffDesc, bytes_len: int, coef_blocks: int, work_bytes: Optional[int] = None) -> np.ndarray:
+    """The device's validity rule per image (TF2_JPEG_REC_* bits; 0: decoded) -- a statement in Python integers.  work_bytes None:
+    a workspace that is large enough."""
+    scan = np.asarray(scan, SCAN_DTYPE).reshape(-1)
+    jrec = np.asarray(jrec, JPEG_DTYPE).reshape(-1)
+    B, nc, (mx, my), S = len(scan), desc.components, desc.eff_sub, desc.subseq
+    slice_ = None if work_bytes is None else (int(work_bytes) // B) & ~7
+    out = np.zeros(B, np.int32)
+    for i, (sc, j) in enumerate(zip(scan, jrec)):
+        off, ln, ri, st = int(sc["byte_off"]), int(sc["byte_len"]), int(sc["restart_interval"]), 0
+        if off < 0 or ln < 0 or ln > HUFF_MAX_BYTES or off > bytes_len or ln > bytes_len - off:
+            st |= REC_BAD_RANGE
+        if (int(sc["components"]), int(sc["sub_x"]), int(sc["sub_y"])) != (nc, mx, my) or not 0 <= ri <= 65535:
+            st |= REC_BAD_SCAN
+        for c in range(nc):
+            if _huff_table(sc["tab"][c]["dc_counts"], sc["tab"][c]["dc_vals"]) is None or \
+               _huff_table(sc["tab"][c]["ac_counts"], sc["tab"][c]["ac_vals"]) is None:
+                st |= REC_BAD_TABLE
+        if not st & REC_BAD_RANGE and slice_ is not None and HUFF_WORK_HEADER + 8 * max(1, -(-ln // S)) > slice_:
+            st |= REC_WORK_TOO_SMALL
+        bw, bh, bo = [int(v) for v in j["bw"]], [int(v) for v in j["bh"]], [int(v) for v in j["block_off"]]
+        for c in range(nc):
+            if not (1 <= bw[c] <= 8192 and 1 <= bh[c] <= 8192):
+                st |= REC_BAD_GRID
+            if bo[c] < 0:
+                st |= REC_BAD_OFFSET
+        if not st & REC_BAD_GRID:
+            if bw[0] % mx or bh[0] % my:
+                st |= REC_BAD_GRID
+            elif nc == 3 and (bw[1] != bw[0] // mx or bw[2] != bw[1] or bh[1] != bh[0] // my or bh[2] != bh[1]):
+                st |= REC_BAD_GRID
+        if not st & (REC_BAD_GRID | REC_BAD_OFFSET):
+            for c in range(nc):
+                if bo[c] > coef_blocks or bw[c] * bh[c] > coef_blocks - bo[c]:
+                    st |= REC_OUT_OF_COEF
+        out[i] = st
+    return out
+
+
+def reference_huff(data, scan, jrec, desc: HuffDesc, coef_blocks: int, coef=None, work_bytes: Optional[int] = None,
+                   tolerant: bool = True):
+    """The statement of tf2_jpeg_huff on the device's own inputs: data (the byte buffer), scan (SCAN_DTYPE [B]), jrec (JPEG_DTYPE
+    [B]) -> (coef int16 [coef_blocks, 64], status int32 [B], rounds int32 [B]).  It runs the parallel algorithm itself:
+    subsequences of desc.subseq bytes in chunks of huff_chunk_lanes, tolerant rounds until no entry state changes, the prefix sums, the
+    strict pass, the record statuses and the zeroing; `rounds` is the rounds used, summed over the chunks.  coef: the buffer as it is
+    before the call (default zeros); only the extents of images without a record bit change.  tolerant False switches the tolerance
+    of the rounds off (a lane stops at the first impossible event): what the rule is there for."""
+    buf = _bytes(data)
+    scan = np.asarray(scan, SCAN_DTYPE).reshape(-1)
+    jrec = np.asarray(jrec, JPEG_DTYPE).reshape(-1)
+    B, nc, (mx, my), S = len(scan), desc.components, desc.eff_sub, desc.subseq
+    out = np.zeros((coef_blocks, 64), np.int16) if coef is None else np.array(coef, np.int16).reshape(coef_blocks, 64)
+    u16 = out.view(np.uint16)
+    status = huff_record_status(scan, jrec, desc, buf.size, coef_blocks, work_bytes)
+    rounds = np.zeros(B, np.int32)
+    for b in range(B):
+        if status[b]:
+            continue
+        sc, j = scan[b], jrec[b]
+        c = _HuffImage()
+        off, c.len = int(sc["byte_off"]), int(sc["byte_len"])
+        c.d = bytes(buf[off:off + c.len])
+        c.tabs = [t for k in range(nc) for t in (_huff_table(sc["tab"][k]["dc_counts"], sc["tab"][k]["dc_vals"]),
+                                                 _huff_table(sc["tab"][k]["ac_counts"], sc["tab"][k]["ac_vals"]))]
+        c.mcub, c.ylum = (1, 1) if nc == 1 else (mx * my + 2, mx * my)
+        c.same = nc == 3 and sc["tab"][0].tobytes() == sc["tab"][1].tobytes() == sc["tab"][2].tobytes()
+        c.ri = int(sc["restart_interval"])
+        c.rim = c.ri * c.mcub
+        bw, bh, bo = [int(v) for v in j["bw"]], [int(v) for v in j["bh"]], [int(v) for v in j["block_off"]]
+        c.mcus_x = bw[0] // mx
+        c.total = c.mcus_x * (bh[0] // my) * c.mcub
+        c.coef, c.cap = u16, 9 * c.len + 64
+
+        def block_of(g, mcub=c.mcub, mcus_x=c.mcus_x, ylum=c.ylum, bw0=bw[0], bo=bo):
+            mcu, bi = divmod(g, mcub)
+            r, q = divmod(mcu, mcus_x)
+            if bi < ylum:
+                y, x = divmod(bi, mx)
+                return bo[0] + (r * my + y) * bw0 + q * mx + x
+            return bo[bi - ylum + 1] + r * mcus_x + q
+        c.block_of = block_of
+        for k in range(nc):
+            out[bo[k]:bo[k] + bw[k] * bh[k]] = 0
+        N = max(1, -(-c.len // S))
+        carry, run, err = (0, 0), (0, 0, 0, 0, 0), 0
+        L = huff_chunk_lanes(S)
+        for first in range(0, N, L):
+            nl = min(L, N - first)
+            ends = [(first + t + 1) * S for t in range(nl)]
+            lasts = [first + t == N - 1 for t in range(nl)]
+            ins = [carry]
+            for t in range(1, nl):
+                at = (first + t) * S
+                ins.append((at + 1 if c.d[at] == 0 and c.d[at - 1] == 0xFF else at, 0))
+            res = [_huff_lane(c, ins[t][0], ins[t][1], ends[t], lasts[t], False, None, tolerant) for t in range(nl)]
+            used = 1
+            for _ in range(1, nl):
+                new = [carry] + [(res[t - 1][0], res[t - 1][1]) for t in range(1, nl)]
+                changed = [t for t in range(nl) if new[t] != ins[t]]
+                if not changed:
+                    break
+                used += 1
+                for t in changed:                                 # (all of them from the exits of the round before)
+                    ins[t] = new[t]
+                res_new = {t: _huff_lane(c, ins[t][0], ins[t][1], ends[t], lasts[t], False, None, tolerant) for t in changed}
+                for t, v in res_new.items():
+                    res[t] = v
+            rounds[b] += used
+            pre = []
+            for t in range(nl):
+                pre.append(run + (0, 0, 0))
+                lm = res[t][2]
+                phase, per = (0 if lm[0] else run[1] % c.mcub), [0, 0, 0]          # slot 0 is this block of the MCU
+                for q in range(c.mcub):
+                    comp = 0 if phase < c.ylum else phase - c.ylum + 1
+                    per[comp] = (per[comp] + lm[2 + q]) & 0xFFFFFFFF
+                    phase = 0 if phase + 1 == c.mcub else phase + 1
+                run = (run[0] + lm[0], lm[1], per[0], per[1], per[2]) if lm[0] else \
+                    (run[0], run[1] + lm[1], (run[2] + per[0]) & 0xFFFFFFFF, (run[3] + per[1]) & 0xFFFFFFFF, (run[4] + per[2]) & 0xFFFFFFFF)
+            carry = (res[nl - 1][0], res[nl - 1][1])
+            for t in range(nl):
+                e = _huff_lane(c, ins[t][0], ins[t][1], ends[t], lasts[t], True, pre[t])[3]
+                if e and not err:
+                    err = e
+            if err:
+                break
+        if err:
+            for k in range(nc):
+                out[bo[k]:bo[k] + bw[k] * bh[k]] = 0
+        status[b] = err
+    return out, status, rounds
+
+
+def pack_bytes_host(files_and_infos, layout: int, sub, pixel_bytes: int = 3, preset: Optional[P.Preset] = None, align: int = 4,
+                    gap: int = 0):
+    """(bytes uint8 [n], scan SCAN_DTYPE [B], jrec, quant, yrec, srec, coef_blocks, planes_bytes, pixels_bytes) of a list of (file
+    bytes, Info): the files' entropy-coded bytes back to back (`gap` bytes of 0xA5 between them) and everything behind the
+    coefficients exactly as `pack_host` lays it out"""
+    items = [(f, i if i is not None else parse(f)) for f, i in files_and_infos]
+    for _, info in items:
+        assert info.status == 0, f"status {info.status}"
+    blank = [(info, np.zeros((info.total_blocks, 64), np.int16)) for _, info in items]
+    hc, jrec, quant, yrec, srec, pbytes, need = pack_host(blank, layout, sub, pixel_bytes, preset, align)
+    parts, scan, at = [], np.zeros(len(items), SCAN_DTYPE), 0
+    for i, (f, info) in enumerate(items):
+        data = _bytes(f)[info.scan_offset:]
+        scan[i] = scan_record(f, info, at)
+        parts += [data, np.full(gap, 0xA5, np.uint8)]
+        at += data.size + gap
+    return np.concatenate(parts), scan, jrec, quant, yrec, srec, len(hc), pbytes, need
+
+
+def pack_bytes(files_and_infos, layout: int, sub, device, pixel_bytes: int = 3, preset: Optional[P.Preset] = None, align: int = 4,
+               subseq_bytes: int = 0, data=None, scan=None, coef=None, jpeg=None, quant=None, planes=None, ycc=None, srcs=None,
+               pixels=None, work=None):
+    """The device inputs of tf2_jpeg_huff and of the tf2_jpeg_idct / tf2_ycc_to_rgb behind it, from `pack_bytes_host`: (data uint8,
+    scan int32 [B, 416], coef int16 [n, 64], jpeg int32 [B, 12], quant int16 [B, 3, 64], planes uint8, ycc int32 [B, 8], srcs int32
+    [B, 10], pixels uint8, work uint8) tensors.  With data= .. work= the caller's tensors are refilled instead (a captured graph reads
+    the same buffers at every replay): the bytes go to the front of `data`, the records fill the tables, `coef`, `planes`, `pixels`
+    and `work` only have to be large enough (`work`: huff_work_bytes of the longest scan)."""
+    import torch
+    hb, hscan, jrec, hq, yrec, srec, nblocks, pbytes, need = pack_bytes_host(files_and_infos, layout, sub, pixel_bytes, preset, align)
+    B = len(hscan)
+
+    def table(t, host, what):
+        host = torch.from_numpy(np.ascontiguousarray(host))
+        if t is None:
+            return host.to(device)
+        assert t.dtype == host.dtype and tuple(t.shape) == tuple(host.shape), f"{what} must be {host.dtype} {tuple(host.shape)}"
+        t.copy_(host)
+        return t
+
+    def room(t, n, what):
+        if t is None:
+            return torch.zeros(n, dtype=torch.uint8, device=device)
+        assert t.dtype == torch.uint8 and t.numel() >= n, f"{what} too small"
+        return t
+    if data is None:
+        data = torch.from_numpy(hb).to(device)
+    else:
+        assert data.dtype == torch.uint8 and data.dim() == 1 and data.numel() >= hb.size, "byte buffer too small"
+        data[:hb.size].copy_(torch.from_numpy(hb))
+    if coef is None:
+        coef = torch.zeros(nblocks, 64, dtype=torch.int16, device=device)
+    else:
+        assert coef.dtype == torch.int16 and coef.dim() == 2 and coef.shape[1] == 64 and coef.shape[0] >= nblocks, "coefficient buffer too small"
+    wneed = huff_work_bytes(HuffDesc(layout, tuple(sub), subseq_bytes), B, int(hscan["byte_len"].max()))
+    return (data, table(scan, Y.records_to_words(hscan, SCAN_WORDS), "scan"), coef, table(jpeg, Y.records_to_words(jrec, JPEG_WORDS), "jpeg"),
+            table(quant, hq.view(np.int16), "quant").view(torch.int16), room(planes, pbytes, "plane buffer"),
+            table(ycc, Y.records_to_words(yrec, Y.YCC_WORDS), "ycc"), table(srcs, Y.records_to_words(srec, P.SRC_WORDS), "srcs"),
+            room(pixels, need, "pixel buffer"), room(work, wneed, "workspace"))
+
+
+class DeviceEntropy:
+    """tf2_jpeg_huff with `desc` (a HuffDesc).
+      run(data, scan, jpeg, coef, work, stream=None, status=None) -> status
+    data: the uint8 device tensor the scans' bytes lie in, scan: int32 [B, 416] (tf2_jpeg_scan records), jpeg: int32 [B, 12]
+    (tf2_jpeg_src), coef: int16 [n, 64] device tensor the blocks are written into, work: uint8 workspace of at least
+    huff_work_bytes(desc, B, longest scan) -- `pack_bytes` makes all five, and DeviceDecoder reads coef / jpeg next.  status: int32
+    [B]: 0, TRUNCATED or BAD_CODE (the image's blocks are zero), or TF2_JPEG_REC_* bits of an image that was left alone.  Enqueued on
+    `stream` (default: the current one); nothing synchronises or allocates beyond the status, which may be passed in."""
+
+    def __init__(self, desc: HuffDesc = HuffDesc()):
+        self.desc = desc
+        self._c = desc.c()
+
+    def run(self, data, scan, jpeg, coef, work, stream=None, status=None):
+        import torch
+        from . import _lib
+        dev = coef.device
+        assert coef.dtype == torch.int16 and coef.is_contiguous() and dev.type == "cuda" and coef.dim() == 2 and coef.shape[1] == 64
+        assert data.dtype == torch.uint8 and data.is_contiguous() and data.device == dev and data.dim() == 1
+        assert work.dtype == torch.uint8 and work.is_contiguous() and work.device == dev
+        assert scan.dtype == torch.int32 and scan.is_contiguous() and scan.device == dev and scan.dim() == 2 and scan.shape[1] == SCAN_WORDS
+        B = scan.shape[0]
+        assert jpeg.dtype == torch.int32 and jpeg.is_contiguous() and jpeg.device == dev and tuple(jpeg.shape) == (B, JPEG_WORDS)
+        stream = stream or torch.cuda.current_stream(dev)
+        with torch.cuda.stream(stream):
+            if status is None:
+                status = torch.empty(B, dtype=torch.int32, device=dev)
+            assert status.dtype == torch.int32 and status.is_contiguous() and status.device == dev and tuple(status.shape) == (B,)
+            _lib.check(_lib.lib().tf2_jpeg_huff(C.byref(self._c), data.data_ptr(), data.numel(), scan.data_ptr(), jpeg.data_ptr(),
+                                                coef.data_ptr(), coef.shape[0], work.data_ptr(), work.numel(), B, status.data_ptr(),
+                                                stream.cuda_stream))
+        return status
+
+    def reference(self, data, scan, jpeg, coef, work_bytes=None):
+        """`reference_huff` on host copies of the tensors (coef: the buffer as it is before the call)"""
+        host = lambda t: t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+        sr = np.ascontiguousarray(host(scan), np.int32).view(SCAN_DTYPE).reshape(-1)
+        jr = np.ascontiguousarray(host(jpeg), np.int32).view(JPEG_DTYPE).reshape(-1)
+        hc = host(coef)
+        return reference_huff(host(data), sr, jr, self.desc, len(hc), hc, work_bytes)
