@@ -412,6 +412,44 @@ tf2_status tf2_roi_crop(const tf2_net* net2, const tf2_preprocess_desc* d, const
                         const tf2_image_src* srcs_dev, int batch, const tf2_roi* rois_dev, int n_slots, int out_q, void* out_dev,
                         int32_t* status_dev, void* hip_stream);
 
+/* ---- Antialiased crops on the device (INTEGRATION.md "Antialiased crops on the device") ----
+ * tf2_roi_crop with the resize of Pillow's Image.resize((OW, OH), BILINEAR, box=(x0, y0, x1, y1)) on the 8-bit source image
+ * (ImagingResample's 8-bit path with a box, reducing_gap None) restated bit for bit: what an enrolment pipeline that crops with
+ * Pillow computes.  The same arguments, structs, records and output layout as tf2_roi_crop; round_resized is validated (0 or 1) and
+ * otherwise ignored, as in tf2_preprocess_aa.  Slot s with record R and source r = srcs_dev[R.image]; along x with n_in = r.w,
+ * n_out = OW, a0 = R.x0, a1 = R.x1 (along y: r.h, OH, R.y0, R.y1), in IEEE double without contraction:
+ *   d = (double)(a1 - a0), the subtraction done in float32, rounded to nearest (Pillow's box is float[4])
+ *   scale = d / n_out; fs = max(scale, 1.0); support = fs; ss = 1.0 / fs
+ *   output index X: center = (double)a0 + (X + 0.5) * scale
+ *     lo = max((int)(center - support + 0.5), 0); hi = min((int)(center + support + 0.5), n_in); n = hi - lo
+ *     w[k], ww, coef[k]: exactly as tf2_preprocess_aa states them above
+ * then tf2_preprocess_aa's two passes (a horizontal pass on source rows to bytes, a vertical pass on those bytes, each
+ * clip((2097152 + sum) >> 22, 0, 255) in int32), v = (r - mean[c]) * scale[c] in float32 on the final byte, and for out_q = 1 the int8
+ * quantisation with net2's 2^-Q0.  tf2_amd.roi.reference_crop_aa is the host statement (tests/golden/pil_resize_box.npz holds
+ * Pillow's own bytes for boxes); the device output is bit-identical to it.  Two consequences:
+ *   - R = (0, 0, w, h) is tf2_preprocess_aa with resize = (OH, OW) and crop (0, 0), bit for bit (d = w exactly, 0.0 + t = t).
+ *   - The filter is centred on the box but clamped at the IMAGE (0 and n_in), not at the box: it reads source pixels outside the box
+ *     and inside the image, up to `support` of them on each side.  The result is Pillow's resize(box=); it is NOT "crop, then
+ *     resize", which would clamp the filter at the box's edge.
+ * Device checks: tf2_roi_crop's rule unchanged (EMPTY alone for image == -1; BAD_IMAGE, BAD_BOX, BAD_SRC in any combination), and
+ * for a slot that rule passes (an image inside the batch with BAD_BOX and BAD_SRC clear) two more bits:
+ *   TF2_ROI_BOX_OUTSIDE unless 0 <= x0, x1 <= w, 0 <= y0 and y1 <= h, compared in double on the float32 values (-0.0 passes).  It is
+ *     Pillow's own precondition, tf2_roi_select with clip = 1 always meets it, and it keeps every (int) conversion above in range.
+ *   TF2_ROI_BAD_SCALE when d > 32 * n_out on either axis (TF2_PREP_AA_MAX_SCALE: at most 65 taps an axis, which bounds one block's LDS
+ *     and time).
+ * A slot with any bit set is all zeros and none of its pixels is read; no read leaves [pixels_dev, pixels_dev + pixels_bytes).
+ * Boxes that leave the image stay with tf2_roi_crop, whose arithmetic and statuses are unchanged.
+ * Host checks: those of tf2_roi_crop.  One kernel of n_slots * ceil(OH / 8) * ceil(OW / 32) blocks of 256 threads on the caller's
+ * stream: a grid that depends on n_slots and net2's image size alone, no allocation, no synchronisation, no atomics, no scratch
+ * (graph-capturable like tf2_roi_crop). */
+enum {
+  TF2_ROI_BOX_OUTSIDE = 16,         /* the box leaves the image (tf2_roi_crop_aa only) */
+  TF2_ROI_BAD_SCALE = 32            /* a side above 32 * the output side (tf2_roi_crop_aa only) */
+};
+tf2_status tf2_roi_crop_aa(const tf2_net* net2, const tf2_preprocess_desc* d, const uint8_t* pixels_dev, size_t pixels_bytes,
+                           const tf2_image_src* srcs_dev, int batch, const tf2_roi* rois_dev, int n_slots, int out_q, void* out_dev,
+                           int32_t* status_dev, void* hip_stream);
+
 /* ---- YCbCr frames on the device (INTEGRATION.md "YCbCr frames on the device") ----
  * The step in front of the three gather calls above: a batch of planar or semi-planar 8-bit YCbCr frames (what a JPEG or a video
  * decoder leaves) -> the interleaved pixels those calls read, written where their tf2_image_src records point.  Needs no net handle.

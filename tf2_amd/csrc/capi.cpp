@@ -335,6 +335,13 @@ tf2_status tf2_roi_crop(const tf2_net* net2, const tf2_preprocess_desc* d, const
   return roi_crop(net2->impl, d, pixels_dev, pixels_bytes, srcs_dev, batch, rois_dev, n_slots, out_q, out_dev, status_dev, stream);
 }
 
+tf2_status tf2_roi_crop_aa(const tf2_net* net2, const tf2_preprocess_desc* d, const uint8_t* pixels_dev, size_t pixels_bytes,
+                           const tf2_image_src* srcs_dev, int batch, const tf2_roi* rois_dev, int n_slots, int out_q, void* out_dev,
+                           int32_t* status_dev, void* stream) {
+  CHECK_NET(net2);
+  return roi_crop_aa(net2->impl, d, pixels_dev, pixels_bytes, srcs_dev, batch, rois_dev, n_slots, out_q, out_dev, status_dev, stream);
+}
+
 tf2_status tf2_ycc_to_rgb(const tf2_ycc_desc* d, const uint8_t* src_dev, size_t src_bytes, const tf2_ycc_src* ycc_dev, uint8_t* pixels_dev,
                           size_t pixels_bytes, const tf2_image_src* srcs_dev, int batch, int32_t* status_dev, void* stream) {
   return ycc_to_rgb(d, src_dev, src_bytes, ycc_dev, pixels_dev, pixels_bytes, srcs_dev, batch, status_dev, stream);

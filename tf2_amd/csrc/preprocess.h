@@ -13,7 +13,8 @@ tf2_status preprocess(const Net& net, const tf2_preprocess_desc* d, const uint8_
 tf2_status preprocess_aa(const Net& net, const tf2_preprocess_desc* d, const uint8_t* pixels, size_t pixels_bytes,
                          const tf2_image_src* srcs, int batch, int out_q, void* out, int32_t* status, void* stream);
 
-// the host checks of tf2_preprocess that tf2_preprocess_aa and tf2_roi_crop (roi_crop.hip) repeats: the refusal's message, "" when there is none
+// the host checks of tf2_preprocess that tf2_preprocess_aa, tf2_roi_crop (roi_crop.hip) and tf2_roi_crop_aa (roi_crop_aa.hip) repeat: the
+// refusal's message, "" when there is none
 std::string preprocess_refusal(const Net& net, const tf2_preprocess_desc* d, int batch, int out_q, bool pointers_ok);
 
 }  // namespace tf2

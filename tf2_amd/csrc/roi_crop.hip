@@ -40,13 +40,6 @@ struct RoiSelectArgs {
   float min_score, expand_w, expand_h;
 };
 
-__device__ __forceinline__ bool finite_f(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
-// the box of the statement is usable: four finite float32 values, both sides at least one source pixel (double on the float32 values)
-__device__ __forceinline__ bool box_ok(float x0, float y0, float x1, float y1) {
-  return finite_f(x0) && finite_f(y0) && finite_f(x1) && finite_f(y1) && (double)x1 - (double)x0 >= 1.0 && (double)y1 - (double)y0 >= 1.0;
-}
-
 __device__ __forceinline__ double clip_to(double v, double limit) { return v < 0.0 ? 0.0 : (v > limit ? limit : v); }
 
 // det row (score, x1, y1, x2, y2) -> the float32 box in pixels of a w x h source; double, every operation rounded separately

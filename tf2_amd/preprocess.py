@@ -270,6 +270,34 @@ def aa_coefs(n_in: int, n_out: int, start: int = 0, count: Optional[int] = None)
     return lo, n, coef
 
 
+def aa_coefs_box(n_in: int, a0, a1, n_out: int):
+    """The coefficient rule of one axis in its box form (csrc/resample_aa.h: aa_axis_box, aa_bounds_box, aa_weight, aa_coef; Pillow's
+    Image.resize(size, BILINEAR, box=...)): n_out samples over the source interval [a0, a1) of an axis of n_in samples, a0 and a1
+    float32.  d = float64(a1 - a0) with the subtraction in float32, scale = d / n_out, center = float64(a0) + (X + 0.5) * scale;
+    support, the clamps at 0 and n_in, weights and coefficients as aa_coefs has them: (lo int64 [n_out], n int64 [n_out],
+    coef int32 [n_out, max n], zero beyond n).  a0 = 0, a1 = n_in is aa_coefs(n_in, n_out)."""
+    a0, a1 = np.float32(a0), np.float32(a1)
+    scale = np.float64(a1 - a0) / np.float64(n_out)
+    fs = max(scale, np.float64(1.0))
+    support, ss = fs, np.float64(1.0) / fs
+    center = np.float64(a0) + (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    lo = np.maximum(np.trunc(center - support + 0.5).astype(np.int64), 0)
+    hi = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), n_in)
+    n = np.maximum(hi - lo, 0)
+    kmax = int(n.max()) if n_out else 0
+    k = np.arange(kmax, dtype=np.int64)[None, :]
+    a = np.abs((((k + lo[:, None]).astype(np.float64) - center[:, None]) + 0.5) * ss)
+    w = np.where((a < 1.0) & (k < n[:, None]), 1.0 - a, 0.0)
+    ww = np.zeros(n_out, np.float64)
+    for j in range(kmax):                                  # in that order, as in aa_coefs
+        ww = ww + w[:, j]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        w = np.where(ww[:, None] != 0, w / ww[:, None], w)
+    coef = np.trunc(w * 4194304.0 + 0.5).astype(np.int32)
+    coef[k >= n[:, None]] = 0
+    return lo, n, coef
+
+
 def resample_pass(src, lo, n, coef) -> np.ndarray:
     """One pass along axis 1 of uint8 [rows, n_in, C]: out[y, X, c] = clip((2^21 + sum_k src[y, lo[X] + k, c] * coef[X, k]) >> 22, 0, 255)
     in int32, as bytes [rows, len(lo), C]"""

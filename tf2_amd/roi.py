@@ -26,7 +26,19 @@ which is bit-identical to them.
                     and, for an image inside the batch, BAD_SRC (the record fails preprocess's size / pitch / offset / extent
                     rule; its resize_* and crop_* fields are not read) in any combination; a slot with a status is zeros.
 
-`DeviceCropper(net2, preset, ...)` runs the device path."""
+Antialiased crops (tf2_roi_crop_aa; csrc/roi_crop_aa.hip): the same table through Pillow's Image.resize((ow, oh), BILINEAR,
+box=(x0, y0, x1, y1)) on the 8-bit source, restated exactly (preprocess.aa_coefs_box is the coefficient rule of a box; tests/golden/
+pil_resize_box.npz holds Pillow's own bytes).
+  crop_pil            Pillow's resize(box=) of one HWC uint8 image.  The filter is centred on the box and clamped at the IMAGE: it reads
+                      pixels outside the box and inside the image, so this is not "crop, then resize".
+  reference_crop_aa   per slot crop_pil of the source's net channels with the slot's float32 box, then (r - mean) * scale in float32 and
+                      the quantisation, in the form of reference_crop.  R = (0, 0, w, h) is preprocess.reference_aa with
+                      resize = (OH, OW) and crop (0, 0), bit for bit.
+  roi_status_aa       roi_status's rule and, for a slot it passes (an image inside the batch, BAD_BOX and BAD_SRC clear), BOX_OUTSIDE
+                      unless 0 <= x0, x1 <= w, 0 <= y0, y1 <= h (float64 on the float32 values) and BAD_SCALE when the float32 side
+                      x1 - x0 > 32 * OW or y1 - y0 > 32 * OH; a slot with a status is zeros.
+
+`DeviceCropper(net2, preset, ...)` runs the device path; antialias=True (or a preset with antialias) takes the antialiased one."""
 import ctypes as C
 from typing import Optional
 
@@ -40,6 +52,7 @@ ROI_DTYPE = np.dtype([("image", "<i4"), ("cls", "<i4"), ("rank", "<i4"), ("score
 ROI_WORDS = ROI_DTYPE.itemsize // 4
 # status bits of a slot that was not cropped (TF2_ROI_*, include/tf2_amd.h)
 EMPTY, BAD_IMAGE, BAD_BOX, BAD_SRC = 1, 2, 4, 8
+BOX_OUTSIDE, BAD_SCALE = 16, 32         # tf2_roi_crop_aa only
 MAX_ROIS, MAX_CLASSES, MAX_TOP_K = 64, 256, 256
 _SRC_BITS = P.BAD_SIZE | P.BAD_PITCH | P.BAD_OFFSET | P.OUT_OF_BUFFER
 
@@ -164,9 +177,70 @@ def reference_crop(pixels, srcs, rois, out_hw, pixel_bytes: int, src_channel, me
     return out, status
 
 
+def crop_pil(img, box, oh: int, ow: int) -> np.ndarray:
+    """Pillow's Image.resize((ow, oh), BILINEAR, box=box) of an HWC (or HW) uint8 image, restated: uint8 [oh, ow, C].  box =
+    (x0, y0, x1, y1) in source pixels, taken as float32 (Pillow's box is float[4]) and inside the image (Pillow's precondition).  The
+    horizontal pass runs first and only on the source rows the vertical pass reads."""
+    img = np.asarray(img, np.uint8)
+    h, w = img.shape[:2]
+    img = img.reshape(h, w, -1)
+    x0, y0, x1, y1 = (np.float32(v) for v in box)
+    xlo, xn, xcoef = P.aa_coefs_box(w, x0, x1, ow)
+    ylo, yn, ycoef = P.aa_coefs_box(h, y0, y1, oh)
+    r0, r1 = int(ylo.min()), int((ylo + yn).max())
+    t = P.resample_pass(img[r0:r1], xlo, xn, xcoef)                                          # [rows, ow, C]
+    return np.swapaxes(P.resample_pass(np.swapaxes(t, 0, 1), ylo - r0, yn, ycoef), 0, 1)     # [oh, ow, C]
+
+
+def roi_status_aa(rois, srcs, pixel_bytes: int, pixels_bytes: int, out_hw) -> np.ndarray:
+    """tf2_roi_crop_aa's validity rule per slot: roi_status, and for a slot it passes BOX_OUTSIDE / BAD_SCALE (the module docstring)"""
+    rois = np.asarray(rois, ROI_DTYPE).reshape(-1)
+    srcs = np.asarray(srcs, P.SRC_DTYPE).reshape(-1)
+    out = roi_status(rois, srcs, pixel_bytes, pixels_bytes)
+    oh, ow = out_hw
+    for s, R in enumerate(rois):
+        if out[s]:
+            continue
+        r = srcs[int(R["image"])]
+        x0, y0, x1, y1 = (np.float32(R[k]) for k in ("x0", "y0", "x1", "y1"))
+        if not (np.float64(x0) >= 0.0 and np.float64(x1) <= np.float64(r["w"]) and np.float64(y0) >= 0.0 and
+                np.float64(y1) <= np.float64(r["h"])):
+            out[s] |= BOX_OUTSIDE
+        if np.float64(x1 - x0) > np.float64(P.AA_MAX_SCALE * ow) or np.float64(y1 - y0) > np.float64(P.AA_MAX_SCALE * oh):
+            out[s] |= BAD_SCALE
+    return out
+
+
+def reference_crop_aa(pixels, srcs, rois, out_hw, pixel_bytes: int, src_channel, mean, scale, round_resized: bool = False,
+                      q0: Optional[int] = None):
+    """tf2_roi_crop_aa's statement on the device's own inputs, in the form of reference_crop: (out, status).  round_resized is not
+    used (the resize result is bytes already)."""
+    pixels = np.asarray(pixels, np.uint8).reshape(-1)
+    srcs = np.asarray(srcs, P.SRC_DTYPE).reshape(-1)
+    rois = np.asarray(rois, ROI_DTYPE).reshape(-1)
+    oh, ow = out_hw
+    status = roi_status_aa(rois, srcs, pixel_bytes, pixels.size, out_hw)
+    out = np.zeros((len(rois), 3, oh, ow), np.float32)
+    m32, s32 = np.asarray(mean, np.float32), np.asarray(scale, np.float32)
+    images = {}
+    for s, R in enumerate(rois):
+        if status[s]:
+            continue
+        i = int(R["image"])
+        if i not in images:
+            images[i] = P.source_image(pixels, srcs[i], pixel_bytes, src_channel)
+        res = crop_pil(images[i], (R["x0"], R["y0"], R["x1"], R["y1"]), oh, ow)
+        out[s] = (np.moveaxis(res, 2, 0).astype(np.float32) - m32[:, None, None]) * s32[:, None, None]
+    if q0 is not None:
+        q = P.quant_input(out, P.trans_of(q0))
+        q[status != 0] = 0
+        return q, status
+    return out, status
+
+
 def whole_image_rois(srcs) -> np.ndarray:
     """one ROI per source record covering the whole image, (0, 0, w, h): reference_crop of it is preprocess.reference with
-    resize = out_hw and no crop"""
+    resize = out_hw and no crop, reference_crop_aa of it preprocess.reference_aa with the same"""
     srcs = np.asarray(srcs, P.SRC_DTYPE).reshape(-1)
     rois = np.zeros(len(srcs), ROI_DTYPE)
     rois["image"] = np.arange(len(srcs))
@@ -209,6 +283,8 @@ class DeviceCropper:
     """tf2_roi_select + tf2_roi_crop for the second network `net2` (a tf2_amd.network.NetWork) with `preset`'s means, scales,
     channel order and round_resized (its resize and crop are not used: the boxes say what is resampled), on sources whose pixel
     bytes are the letters of src_order.  num_classes / top_k: the layout of the detector's det [B, C, K, 5] / counts [B, C].
+    antialias: crop with tf2_roi_crop_aa (Pillow's resize(box=); the boxes must lie inside their images, as clip=True makes them)
+    instead of tf2_roi_crop; None: preset.antialias.  crop, __call__, reference_crop and reference follow the choice.
       select(det, counts, srcs, stream=None, rois=None, roi_counts=None) -> (rois int32 [B * max_rois, 8], roi_counts int32 [B])
       crop(pixels, srcs, rois, out="q" | "f32", stream=None, images=None, status=None) -> (images [S, 3, h, w], status int32 [S])
       __call__(det, counts, pixels, srcs, out="q", stream=None, ...) -> (images, status, rois, roi_counts)
@@ -219,9 +295,11 @@ class DeviceCropper:
     every replay)."""
 
     def __init__(self, net2, preset: P.Preset, src_order: str = "RGB", num_classes: int = 21, top_k: int = 200, classes=(15,),
-                 min_score: float = 0.5, max_rois: int = 4, expand=(1.0, 1.0), square: bool = False, clip: bool = True):
+                 min_score: float = 0.5, max_rois: int = 4, expand=(1.0, 1.0), square: bool = False, clip: bool = True,
+                 antialias: Optional[bool] = None):
         from . import _lib
         self.net, self.preset, self.src_order = net2, preset, src_order
+        self.antialias = bool(preset.antialias if antialias is None else antialias)
         self.num_classes, self.top_k, self.classes = int(num_classes), int(top_k), tuple(int(c) for c in classes)
         self.min_score, self.max_rois, self.expand = float(min_score), int(max_rois), (float(expand[0]), float(expand[1]))
         self.square, self.clip = bool(square), bool(clip)
@@ -275,9 +353,9 @@ class DeviceCropper:
                 status = torch.empty(S, dtype=torch.int32, device=dev)
             assert images.dtype == dtype and images.is_contiguous() and images.device == dev and tuple(images.shape) == (S, 3) + self.out_hw
             assert status.dtype == torch.int32 and status.is_contiguous() and status.device == dev and tuple(status.shape) == (S,)
-            _lib.check(_lib.lib().tf2_roi_crop(self.net._h, C.byref(self.desc), pixels.data_ptr(), pixels.numel(), srcs.data_ptr(), B,
-                                               rois.data_ptr(), S, int(out == "q"), images.data_ptr(), status.data_ptr(),
-                                               stream.cuda_stream))
+            fn = _lib.lib().tf2_roi_crop_aa if self.antialias else _lib.lib().tf2_roi_crop
+            _lib.check(fn(self.net._h, C.byref(self.desc), pixels.data_ptr(), pixels.numel(), srcs.data_ptr(), B, rois.data_ptr(), S,
+                          int(out == "q"), images.data_ptr(), status.data_ptr(), stream.cuda_stream))
         return images, status
 
     def __call__(self, det, counts, pixels, srcs, out: str = "q", stream=None, rois=None, roi_counts=None, images=None, status=None):
@@ -292,12 +370,13 @@ class DeviceCropper:
                                 self.square, self.clip)
 
     def reference_crop(self, pixels, srcs, rois, out: str = "q"):
-        """reference_crop on host copies of the tensors, with net2's Q0 for out="q" """
+        """reference_crop -- reference_crop_aa when antialias -- on host copies of the tensors, with net2's Q0 for out="q" """
         p = pixels.cpu().numpy() if hasattr(pixels, "cpu") else np.asarray(pixels)
         r = rois if isinstance(rois, np.ndarray) and rois.dtype == ROI_DTYPE else rois_to_host(rois)
-        return reference_crop(p, _srcs_host(srcs), r, self.out_hw, len(self.src_order), P.src_channels(self.preset, self.src_order),
-                              np.float32(self.preset.mean), np.float32(self.preset.scale), self.preset.round_resized,
-                              int(self.net.q[0, 0]) if out == "q" else None)
+        fn = reference_crop_aa if self.antialias else reference_crop
+        return fn(p, _srcs_host(srcs), r, self.out_hw, len(self.src_order), P.src_channels(self.preset, self.src_order),
+                  np.float32(self.preset.mean), np.float32(self.preset.scale), self.preset.round_resized,
+                  int(self.net.q[0, 0]) if out == "q" else None)
 
     def reference(self, det, counts, pixels, srcs, out: str = "q"):
         """The statement of __call__ on host copies of the same inputs: (images, status, rois ROI_DTYPE, roi_counts)"""

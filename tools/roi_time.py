@@ -14,7 +14,16 @@ captured graph per stream, replayed round robin), SSD300 and SqueezeNet 1.1 with
   detector      tf2_preprocess + tf2_ssd_run
   cascade       the same + select + crop + SqueezeNet 1.1 on the crops + tf2_emb_match against --gallery rows
 (min_score is the detector's conf_thresh and every class is taken, so the synthetic detector fills the slots; cascade_filled_slots
-says how many it filled).  Prints one JSON line; --out writes it to a file as well.  `--kernel-only` stops after the event times."""
+says how many it filled).  Prints one JSON line; --out writes it to a file as well.  `--kernel-only` stops after the event times.
+
+`--antialias` measures the antialiased crop instead (tf2_roi_crop_aa, roi_crop_aa.hip) and writes profiles/roi_aa_time_b32.json unless
+--out names another file: on the same table and sources, the same way,
+  crop_aa        one tf2_roi_crop_aa call, int8 and float32
+  crop           one tf2_roi_crop call on the same table
+  preprocess_aa  one tf2_preprocess_aa call producing the same number of 227 x 227 outputs from whole images: the yardstick, the same
+                 tile kernel at the whole image's scale
+crop_aa_over_preprocess_aa and crop_aa_over_crop, the ratios of the medians, the mean scale of the table's boxes, and the images/s of
+the cascade with --inflight batches in flight with the plain and with the antialiased crop (their timed repeats alternate)."""
 import argparse
 import json
 import os
@@ -39,6 +48,7 @@ def main():
     ap.add_argument("--inflight", type=int, default=4)
     ap.add_argument("--gallery", type=int, default=1000)
     ap.add_argument("--kernel-only", action="store_true")
+    ap.add_argument("--antialias", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -103,6 +113,8 @@ def main():
     timed(lambda k: crop.select(det_d, counts_d, srcs[k % n_sets][1], rois=rois, roi_counts=roi_n), "select")
     torch.cuda.synchronize()
     assert int(roi_n.sum()) == B * M, "the synthetic det must fill every slot"
+    if a.antialias:
+        return antialias(a, res, timed, face, make_net, srcs, rois, crop, rng)
     big = np.zeros((B, 256, 256, 5), np.float32)
     big[..., 0] = rng.uniform(0.0, 1.0, big.shape[:3])
     big[..., 1:3], big[..., 3:5] = 0.25, 0.75
@@ -198,7 +210,102 @@ def main():
     finish(res, a)
 
 
+def antialias(a, res, timed, face, make_net, srcs, rois, crop, rng):
+    """the --antialias measurement (the module docstring); rois: the table `crop.select` left on the device"""
+    import torch
+    from tf2_amd import config as cfg, embed as E, preprocess as P, roi as R, ssd, synth
+    from tf2_amd.network import Runner
+    from dataclasses import replace
+    dev, B, M, n_sets = "cuda:0", a.batch, a.max_rois, len(srcs)
+    crop_aa = R.DeviceCropper(face, P.SQUEEZENET, "RGB", classes=(15,), min_score=0.5, max_rois=M, antialias=True)
+    table = R.rois_to_host(rois)
+    res["mean_box_scale_xy"] = [round(float(np.mean((table["x1"] - table["x0"]) / 227.0)), 3),
+                                round(float(np.mean((table["y1"] - table["y0"]) / 227.0)), 3)]
+    res["whole_image_scale_xy"] = [round(a.src_w / 227.0, 3), round(a.src_h / 227.0, 3)]
+    pre_aa = replace(P.SQUEEZENET, antialias=True)
+    pp = P.Preprocessor(face, pre_aa, "RGB")
+    whole = []
+    for px, sr in srcs:
+        rec = sr.cpu().numpy().view(P.SRC_DTYPE).reshape(-1).copy()
+        rec["resize_h"], rec["resize_w"], rec["crop_y"], rec["crop_x"] = 227, 227, 0, 0
+        rec = np.repeat(rec, M)
+        whole.append((px, torch.from_numpy(rec.view(np.int32).reshape(len(rec), P.SRC_WORDS).copy()).to(dev)))
+    for out, dtype in (("q", torch.int8), ("f32", torch.float32)):
+        buf = torch.empty(B * M, 3, 227, 227, dtype=dtype, device=dev)
+        st = torch.empty(B * M, dtype=torch.int32, device=dev)
+        for tag, c in ((f"crop_aa_{out}", crop_aa), (f"crop_{out}", crop)):
+            timed(lambda k: c.crop(*srcs[k % n_sets], rois, out=out, images=buf, status=st), tag)
+            torch.cuda.synchronize()
+            assert int(st.abs().sum()) == 0
+        timed(lambda k: pp(*whole[k % n_sets], out=out), f"preprocess_aa_{out}")
+        res[f"crop_aa_over_preprocess_aa_{out}"] = round(res[f"crop_aa_{out}_us"] / res[f"preprocess_aa_{out}_us"], 4)
+        res[f"crop_aa_over_crop_{out}"] = round(res[f"crop_aa_{out}_us"] / res[f"crop_{out}_us"], 4)
+    if a.kernel_only:
+        return finish(res, a)
+
+    # -- the cascade with batches in flight, plain and antialiased crops; the timed repeats of the two alternate
+    t300 = cfg.ssd300_tables()
+    net300 = make_net(t300, np.array(synth.synth_q_values(t300, 5, spread=1)), 0)
+    pp300 = P.Preprocessor(net300, P.SSD300, "RGB")
+    g = rng.normal(0, 1, (a.gallery, 128)).astype(np.float32)
+    gallery = torch.from_numpy(g / np.linalg.norm(g, axis=1, keepdims=True).astype(np.float32)).to(dev)
+    croppers = {name: R.DeviceCropper(face, P.SQUEEZENET, "RGB", classes=tuple(range(1, 21)), min_score=0.01, max_rois=M, antialias=aa)
+                for name, aa in (("cascade", False), ("cascade_aa", True))}
+    dets = [ssd.DeviceDetector(net300, net300.plan, ssd.VOC) for _ in range(a.inflight)]
+    runners = [Runner(None, face) for _ in range(a.inflight)]
+    matchers = [E.DeviceMatcher(face, 5) for _ in range(a.inflight)]
+    streams = [torch.cuda.Stream() for _ in range(a.inflight)]
+    graphs, keep = {}, {}
+
+    def cascade(name, i, k):
+        px, sr = srcs[k]
+        d, c = dets[i].run(pp300(px, sr, out="q")[0])
+        crops, st, _, n = croppers[name](d, c, px, sr, out="q")
+        keep[name, k] = (n, st)
+        return matchers[i].match(runners[i].run_batch(crops, concurrency=1), gallery)
+
+    for name in croppers:
+        for k in range(n_sets):
+            i = k % a.inflight
+            streams[i].wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(streams[i]):
+                cascade(name, i, k)                                # warm the launch plans of this stream's workspaces
+                torch.cuda.current_stream().synchronize()
+                gr = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gr, stream=streams[i]):
+                    cascade(name, i, k)
+            torch.cuda.current_stream().wait_stream(streams[i])
+            graphs[name, k] = gr
+    torch.cuda.synchronize()
+
+    def run(name, n):
+        for k in range(n):
+            with torch.cuda.stream(streams[k % a.inflight]):
+                graphs[name, k % n_sets].replay()
+
+    rates = {name: [] for name in croppers}
+    for name in croppers:
+        run(name, a.warmup)
+    torch.cuda.synchronize()
+    for _ in range(3):
+        for name in croppers:
+            t0 = time.perf_counter()
+            run(name, a.steps)
+            torch.cuda.synchronize()
+            rates[name].append(B * a.steps / (time.perf_counter() - t0))
+    for name in croppers:
+        res[f"{name}_inflight_images_per_s"] = round(float(np.median(rates[name])), 1)
+        res[f"{name}_inflight_images_per_s_min_max"] = [round(min(rates[name]), 1), round(max(rates[name]), 1)]
+        res[f"{name}_filled_slots"] = int(sum(int(keep[name, k][0].sum()) for k in range(n_sets))) // n_sets
+        bits = torch.cat([keep[name, k][1] for k in range(n_sets)]).cpu().numpy()
+        assert set(np.unique(bits).tolist()) <= {0, R.EMPTY}, np.unique(bits)         # clipped boxes: nothing refused
+    res["cascade_aa_over_cascade"] = round(res["cascade_aa_inflight_images_per_s"] / res["cascade_inflight_images_per_s"], 4)
+    finish(res, a)
+
+
 def finish(res, a):
+    if a.antialias and not a.out:
+        a.out = os.path.join(ROOT, "profiles", "roi_aa_time_b32.json")
     print(json.dumps(res))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
