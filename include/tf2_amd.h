@@ -450,6 +450,77 @@ tf2_status tf2_roi_crop_aa(const tf2_net* net2, const tf2_preprocess_desc* d, co
                            const tf2_image_src* srcs_dev, int batch, const tf2_roi* rois_dev, int n_slots, int out_q, void* out_dev,
                            int32_t* status_dev, void* hip_stream);
 
+/* ---- Aligned crops on the device (INTEGRATION.md "Aligned crops on the device") ----
+ * The same select / crop split for windows that are not upright: tf2_roi_fit turns K landmarks a slot into a table of tf2_roi_xform
+ * records in device memory, tf2_roi_warp resamples each record's affine window out of the SOURCE pixels into one image of net2's
+ * input.  The face network of the cascade is calibrated and evaluated on aligned faces (a similarity warp that puts eyes, nose and
+ * mouth corners on a fixed template); callers may also fill the table themselves (rotated boxes, a transform of their own).
+ * tf2_amd.align.reference_fit / reference_warp are the host statement; every device output is bit-identical to them.
+ * The record: m maps output pixel centres to source coordinates in Pillow's Image.AFFINE convention (pixel i covers [i, i + 1), as
+ * in tf2_roi); image == -1 is the empty slot.  56 bytes; the table must be 8-byte aligned.
+ * Fit, per slot s with R = rois_dev[s] and the float32 landmarks lmk_dev[s][i] = (u_i, v_i), i = 0 .. K-1 (K = n_points): space 0
+ * takes them as source pixels, sx_i = u_i, sy_i = v_i; space 1 as relative to the slot's box, sx_i = x0 + u_i * (x1 - x0),
+ * sy_i = y0 + v_i * (y1 - y0).  The template (tx_i, ty_i) = tpl[i] is in output pixels of net2's input.  The fit is the
+ * least-squares similarity without reflection, landmarks -> template, inverted into the output -> source map; it is stated with
+ * + - * / alone in IEEE double from the float32 values, every operation rounded separately (no contraction), sums taken in index
+ * order from 0.0:
+ *   mx = (sum sx_i) / K, my = (sum sy_i) / K, ux = (sum tx_i) / K, uy = (sum ty_i) / K
+ *   px = sx_i - mx, py = sy_i - my, qx = tx_i - ux, qy = ty_i - uy
+ *   var += px*px + py*py;   c += px*qx + py*qy;   s += px*qy - py*qx        (i = 0 .. K-1)
+ *   A = c / var;  B = s / var;  n = A*A + B*B;  a = A / n;  b = -B / n
+ *   m = { a, -b, (mx - a*ux) + b*uy,   b, a, (my - b*ux) - a*uy }
+ * status_dev[s] receives 0 or TF2_ROI_* bits: EMPTY alone for R.image == -1; otherwise BAD_BOX when space == 1 and the box fails the
+ * validity rule of tf2_roi_crop, and TF2_ROI_BAD_LANDMARKS when one of the 2 * K float32 coordinates is not finite; with both clear
+ * the fit runs and BAD_LANDMARKS is set when var > 0 fails, when n > 0 fails or when any of the six results is not finite.  (The
+ * image index is not judged here: tf2_roi_warp does.)  A slot with status 0 gets { R.image, 0, m }; any other gets the empty record:
+ * image -1, reserved 0, every m equal to +0.0.  Every slot is written by every call with plain stores.
+ * Host checks of fit (TF2_ERR_ARG with a message, before any device call): desc size, n_points in 2..16, space 0 or 1, the
+ * 2 * n_points template values finite, a template variance sum(qx*qx + qy*qy) > 0 (double, as above), n_slots >= 1, non-null
+ * pointers, xf_dev 8-byte aligned.  One kernel of ceil(n_slots / 64) blocks of 64 threads, a thread a slot.
+ * Warp, per slot s with record T = xf_dev[s], m = T.m, source r = srcs_dev[T.image] and output pixel (y, x) of net2's OH x OW input:
+ * Pillow's Image.transform((OW, OH), Image.AFFINE, m, resample=BILINEAR) on the 8-bit source (ImagingGenericTransform with
+ * affine_transform and the 8-bit bilinear filter) restated bit for bit, in double, every operation rounded separately:
+ *   xin = x + 0.5; yin = y + 0.5
+ *   fx = (m0*xin + m1*yin) + m2;   fy = (m3*xin + m4*yin) + m5
+ *   inside iff fx >= 0 && fx < r.w && fy >= 0 && fy < r.h     (a NaN is outside; no integer conversion happens before this test)
+ *   outside: the byte is 0 in every channel (Pillow's fill)
+ *   inside:  fx -= 0.5; fy -= 0.5; X = floor(fx); dx = fx - X; Y = floor(fy); dy = fy - Y          (X, Y >= -1)
+ *            xa = clamp(X, 0, w-1); xb = clamp(X+1, 0, w-1); ya = clamp(Y, 0, h-1)
+ *            v1 = p[ya][xa] + (p[ya][xb] - p[ya][xa]) * dx                                         (the difference in integers)
+ *            v2 = (Y + 1 < h) ? p[Y+1][xa] + (p[Y+1][xb] - p[Y+1][xa]) * dx : v1
+ *            byte = (uint8)(v1 + (v2 - v1) * dy)                                                   (truncation)
+ * then v = ((float)byte - mean[c]) * scale[c] in float32 -- a fill byte 0 goes through the same line -- and for out_q = 1 the int8
+ * quantisation with net2's 2^-Q0, as tf2_roi_crop.  There is no antialiasing (Pillow's transform has none; tf2_roi_crop_aa stays the
+ * answer for upright boxes) and no scale limit: the cost per output pixel is constant.  The arguments, the desc, the source records
+ * and the output layout are tf2_roi_crop's with xf_dev in place of rois_dev; round_resized is validated and otherwise ignored.
+ * Device checks of warp, per slot, before a pixel is read: EMPTY alone for image == -1; otherwise BAD_IMAGE (outside 0..batch-1; no
+ * source record is read), BAD_SRC (tf2_roi_crop's rule) and TF2_ROI_BAD_MATRIX unless all six m are finite, in any combination.  A
+ * slot with any bit set is all zeros and none of its pixels is read; no read leaves [pixels_dev, pixels_dev + pixels_bytes).
+ * Host checks of warp: those of tf2_roi_crop, and xf_dev 8-byte aligned.  One kernel of n_slots * ceil(OH * OW / 1024) blocks of 256
+ * threads on the caller's stream: a grid that depends on n_slots and net2's image size alone, no allocation, no synchronisation, no
+ * atomics, no scratch (graph-capturable: detect + select + fit + warp + embed + match replays on refilled buffers). */
+#define TF2_ROI_FIT_MAX_POINTS 16
+typedef struct tf2_roi_xform {      /* one slot of the transform table, 56 bytes, 8-byte aligned, in DEVICE memory */
+  int32_t image;                    /* index into srcs_dev; -1: empty slot */
+  int32_t reserved;                 /* 0 */
+  double m[6];                      /* source x = m0*(x+.5) + m1*(y+.5) + m2, source y = m3*(x+.5) + m4*(y+.5) + m5 */
+} tf2_roi_xform;
+typedef struct tf2_roi_fit_desc {
+  uint32_t size;                    /* sizeof(tf2_roi_fit_desc) */
+  int32_t n_points;                 /* K, 2..16 */
+  float tpl[TF2_ROI_FIT_MAX_POINTS][2];   /* (x, y) of the first K points in output pixels of net2's input; finite, not all equal */
+  int32_t space;                    /* 0: landmarks in source pixels; 1: relative to the slot's box */
+} tf2_roi_fit_desc;
+enum {
+  TF2_ROI_BAD_LANDMARKS = 64,       /* a landmark not finite, or a degenerate fit (tf2_roi_fit only) */
+  TF2_ROI_BAD_MATRIX = 128          /* an entry of m not finite (tf2_roi_warp only) */
+};
+tf2_status tf2_roi_fit(const tf2_roi_fit_desc* d, const tf2_roi* rois_dev, const float* lmk_dev, int n_slots, tf2_roi_xform* xf_dev,
+                       int32_t* status_dev, void* hip_stream);
+tf2_status tf2_roi_warp(const tf2_net* net2, const tf2_preprocess_desc* d, const uint8_t* pixels_dev, size_t pixels_bytes,
+                        const tf2_image_src* srcs_dev, int batch, const tf2_roi_xform* xf_dev, int n_slots, int out_q, void* out_dev,
+                        int32_t* status_dev, void* hip_stream);
+
 /* ---- YCbCr frames on the device (INTEGRATION.md "YCbCr frames on the device") ----
  * The step in front of the three gather calls above: a batch of planar or semi-planar 8-bit YCbCr frames (what a JPEG or a video
  * decoder leaves) -> the interleaved pixels those calls read, written where their tf2_image_src records point.  Needs no net handle.

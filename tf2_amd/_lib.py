@@ -87,6 +87,16 @@ class RoiDesc(C.Structure):
                 ("square", C.c_int32), ("clip", C.c_int32)]
 
 
+class RoiXform(C.Structure):
+    """tf2_roi_xform (include/tf2_amd.h): one slot of the transform table, in device memory."""
+    _fields_ = [("image", C.c_int32), ("reserved", C.c_int32), ("m", C.c_double * 6)]
+
+
+class RoiFitDesc(C.Structure):
+    """tf2_roi_fit_desc (include/tf2_amd.h)."""
+    _fields_ = [("size", C.c_uint32), ("n_points", C.c_int32), ("tpl", (C.c_float * 2) * 16), ("space", C.c_int32)]
+
+
 class YccSrc(C.Structure):
     """tf2_ycc_src (include/tf2_amd.h): the planes of one image, in device memory."""
     _fields_ = [("off_y", C.c_int64), ("off_cb", C.c_int64), ("off_cr", C.c_int64), ("pitch_y", C.c_int32), ("pitch_c", C.c_int32)]
@@ -277,6 +287,8 @@ def lib() -> C.CDLL:
     L.tf2_roi_select.argtypes = [C.POINTER(RoiDesc), vp, vp, vp, C.c_int, vp, vp, vp]
     L.tf2_roi_crop.argtypes = [vp, C.POINTER(PreprocessDesc), vp, sz, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp]
     L.tf2_roi_crop_aa.argtypes = L.tf2_roi_crop.argtypes
+    L.tf2_roi_fit.argtypes = [C.POINTER(RoiFitDesc), vp, vp, C.c_int, vp, vp, vp]
+    L.tf2_roi_warp.argtypes = L.tf2_roi_crop.argtypes
     L.tf2_ycc_to_rgb.argtypes = [C.POINTER(YccDesc), vp, sz, vp, vp, sz, vp, C.c_int, vp, vp]
     L.tf2_jpeg_parse.argtypes = [vp, sz, C.POINTER(JpegInfo)]
     L.tf2_jpeg_entropy.argtypes = [vp, sz, C.POINTER(JpegInfo), vp, sz, i32p]
@@ -359,7 +371,7 @@ EXPORTED = [
     "tf2_net_packed_adopt", "tf2_net_bind_device", "tf2_net_workspace_size", "tf2_net_logits_size", "tf2_net_reload_options", "tf2_net_run",
     "tf2_net_run_q", "tf2_net_run_ex", "tf2_net_run_stats", "tf2_net_poll_error", "tf2_net_describe_launches", "tf2_net_describe_workspace", "tf2_net_read_layer", "tf2_net_profile", "tf2_net_profile_read", "tf2_net_profile_loop_read", "tf2_topk",
     "tf2_ssd_create", "tf2_ssd_destroy", "tf2_ssd_workspace_size", "tf2_ssd_detect_scratch_size", "tf2_ssd_run", "tf2_ssd_detect",
-    "tf2_preprocess", "tf2_preprocess_aa", "tf2_roi_select", "tf2_roi_crop", "tf2_roi_crop_aa", "tf2_ycc_to_rgb", "tf2_jpeg_parse", "tf2_jpeg_entropy", "tf2_jpeg_idct", "tf2_jpeg_scan_fill", "tf2_jpeg_huff_work_bytes", "tf2_jpeg_huff", "tf2_cls_create", "tf2_cls_destroy", "tf2_cls_run",
+    "tf2_preprocess", "tf2_preprocess_aa", "tf2_roi_select", "tf2_roi_crop", "tf2_roi_crop_aa", "tf2_roi_fit", "tf2_roi_warp", "tf2_ycc_to_rgb", "tf2_jpeg_parse", "tf2_jpeg_entropy", "tf2_jpeg_idct", "tf2_jpeg_scan_fill", "tf2_jpeg_huff_work_bytes", "tf2_jpeg_huff", "tf2_cls_create", "tf2_cls_destroy", "tf2_cls_run",
     "tf2_det_eval_create", "tf2_det_eval_destroy", "tf2_det_eval_store_size", "tf2_det_eval_store_init", "tf2_det_eval_run",
     "tf2_det_eval_summarise",
     "tf2_emb_create", "tf2_emb_destroy", "tf2_emb_scratch_size", "tf2_emb_embed", "tf2_emb_match",

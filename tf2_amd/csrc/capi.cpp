@@ -11,6 +11,7 @@
 #include "embed_match.h"
 #include "embed_roc.h"
 #include "roi_crop.h"
+#include "roi_warp.h"
 #include "ycc_convert.h"
 #include "jpeg_idct.h"
 #include "jpeg_huff.h"
@@ -340,6 +341,18 @@ tf2_status tf2_roi_crop_aa(const tf2_net* net2, const tf2_preprocess_desc* d, co
                            int32_t* status_dev, void* stream) {
   CHECK_NET(net2);
   return roi_crop_aa(net2->impl, d, pixels_dev, pixels_bytes, srcs_dev, batch, rois_dev, n_slots, out_q, out_dev, status_dev, stream);
+}
+
+tf2_status tf2_roi_fit(const tf2_roi_fit_desc* d, const tf2_roi* rois_dev, const float* lmk_dev, int n_slots, tf2_roi_xform* xf_dev,
+                       int32_t* status_dev, void* stream) {
+  return roi_fit(d, rois_dev, lmk_dev, n_slots, xf_dev, status_dev, stream);
+}
+
+tf2_status tf2_roi_warp(const tf2_net* net2, const tf2_preprocess_desc* d, const uint8_t* pixels_dev, size_t pixels_bytes,
+                        const tf2_image_src* srcs_dev, int batch, const tf2_roi_xform* xf_dev, int n_slots, int out_q, void* out_dev,
+                        int32_t* status_dev, void* stream) {
+  CHECK_NET(net2);
+  return roi_warp(net2->impl, d, pixels_dev, pixels_bytes, srcs_dev, batch, xf_dev, n_slots, out_q, out_dev, status_dev, stream);
 }
 
 tf2_status tf2_ycc_to_rgb(const tf2_ycc_desc* d, const uint8_t* src_dev, size_t src_bytes, const tf2_ycc_src* ycc_dev, uint8_t* pixels_dev,
