@@ -10,8 +10,6 @@ import vmcnt_check  # noqa: E402
 
 
 def test_roi_warp_kernels_use_no_private_segment():
-    vmcnt_check.build_isa()
-    txt = open(os.path.join(vmcnt_check.ISA_DIR, "roi_warp.s")).read()
-    seg = {m.group(1): int(m.group(2)) for m in re.finditer(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)", txt)}
+    seg, lds, txt = vmcnt_check.kernel_segments("roi_warp")
     assert sum("roi_fit_kernel" in k for k in seg) == 1 and sum("roi_warp_kernel" in k for k in seg) == 4, seg   # int8 / float32 x vector / scalar stores
     assert len(seg) == 5 and all(v == 0 for v in seg.values()), seg

@@ -203,9 +203,7 @@ def test_classify_kernel_compiles_without_scratch():
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
     import vmcnt_check
-    vmcnt_check.build_isa()
-    txt = open(os.path.join(vmcnt_check.ISA_DIR, "classify.s")).read()
-    seg = {m.group(1): int(m.group(2)) for m in re.finditer(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)", txt)}
+    seg, lds, txt = vmcnt_check.kernel_segments("classify")
     names = [k for k in seg if "classify_kernel" in k]
     assert len(names) == 1 and len(seg) == 1, seg
     assert seg[names[0]] == 0, seg

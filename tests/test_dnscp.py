@@ -280,7 +280,5 @@ def test_kernels_compile_without_scratch():
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import vmcnt_check
-    isa_dir = os.path.dirname(vmcnt_check.build_isa()[0])
-    txt = open(os.path.join(isa_dir, "weight_dnscp.s")).read()
-    sizes = re.findall(r"\.private_segment_fixed_size:\s*(\d+)", txt)
+    sizes = list(vmcnt_check.kernel_segments("weight_dnscp")[0].values())
     assert len(sizes) == 7 and all(int(s) == 0 for s in sizes), sizes

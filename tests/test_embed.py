@@ -262,9 +262,7 @@ def test_embed_match_kernels_compile_without_scratch():
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
     import vmcnt_check
-    vmcnt_check.build_isa()
-    txt = open(os.path.join(vmcnt_check.ISA_DIR, "embed_match.s")).read()
-    seg = {m.group(1): int(m.group(2)) for m in re.finditer(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)", txt)}
+    seg, lds, txt = vmcnt_check.kernel_segments("embed_match")
     assert len(seg) == 3, seg
     for kernel in ("embed_kernel", "match_slab_kernel", "match_merge_kernel"):
         names = [k for k in seg if kernel in k]

@@ -309,9 +309,7 @@ def test_act_fidelity_kernels_compile_without_scratch():
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
     import vmcnt_check
-    vmcnt_check.build_isa()
-    txt = open(os.path.join(vmcnt_check.ISA_DIR, "act_fidelity.s")).read()
-    seg = {m.group(1): int(m.group(2)) for m in re.finditer(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)", txt)}
+    seg, lds, txt = vmcnt_check.kernel_segments("act_fidelity")
     assert len(seg) == 2, seg
     for kernel in ("fid_rows_kernel", "fid_image_kernel"):
         names = [k for k in seg if kernel in k]

@@ -235,8 +235,5 @@ def test_quantised_stream_writes_a_4bit_file_of_codes():
 def test_kernels_compile_without_scratch():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import vmcnt_check
-    isa_dir = os.path.dirname(vmcnt_check.build_isa()[0])
-    txt = open(os.path.join(isa_dir, "weight_inq.s")).read()
-    import re
-    sizes = re.findall(r"\.private_segment_fixed_size:\s*(\d+)", txt)
+    sizes = list(vmcnt_check.kernel_segments("weight_inq")[0].values())
     assert len(sizes) == 6 and all(int(s) == 0 for s in sizes), sizes

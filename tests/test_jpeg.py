@@ -482,9 +482,7 @@ def test_reference_idct_wraps_like_python_integers():
 
 def test_jpeg_kernels_compile_without_scratch():
     import vmcnt_check
-    vmcnt_check.build_isa()
-    txt = open(os.path.join(vmcnt_check.ISA_DIR, "jpeg_idct.s")).read()
-    seg_ = {m.group(1): int(m.group(2)) for m in re.finditer(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)", txt)}
+    seg_, lds, txt = vmcnt_check.kernel_segments("jpeg_idct")
     names = [k for k in seg_ if "jpeg_idct_kernel" in k]
     assert len(names) == 2, seg_                                   # one and three components
     assert all(seg_[k] == 0 for k in names), seg_

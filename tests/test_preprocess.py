@@ -260,9 +260,7 @@ def test_preprocess_kernels_compile_without_scratch():
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
     import vmcnt_check
-    vmcnt_check.build_isa()
-    txt = open(os.path.join(vmcnt_check.ISA_DIR, "preprocess.s")).read()
-    seg = {m.group(1): int(m.group(2)) for m in re.finditer(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)", txt)}
+    seg, lds, txt = vmcnt_check.kernel_segments("preprocess")
     names = [k for k in seg if "preprocess_kernel" in k]
     assert len(names) == 4, seg                                    # int8 / float32 output, vector / byte stores
     assert all(seg[k] == 0 for k in names), seg

@@ -257,12 +257,9 @@ def test_reference_aa_is_resize_pil_then_mean_and_scale():
 
 def test_preprocess_aa_kernels_compile_without_scratch():
     import vmcnt_check
-    vmcnt_check.build_isa()
-    txt = open(os.path.join(vmcnt_check.ISA_DIR, "preprocess_aa.s")).read()
-    seg = {m.group(1): int(m.group(2)) for m in re.finditer(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)", txt)}
-    names = [k for k in seg if "preprocess_aa_kernel" in k]
+    seg, lds, txt = vmcnt_check.kernel_segments("preprocess_aa")
+    names = [k for k in seg if "aa_tile_kernel" in k]
     assert len(names) == 2, seg                                    # int8 / float32 output
     assert all(seg[k] == 0 for k in names), seg
     assert "scratch_" not in txt.split("amdhsa.kernels")[0]
-    lds = [int(v) for v in re.findall(r"\.group_segment_fixed_size:\s+(\d+)", txt)]
     assert lds and max(lds) <= 16384, lds                          # bounded whatever the scale: coefficients 40 x 65, two chunks

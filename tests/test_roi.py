@@ -323,9 +323,7 @@ def test_roi_kernels_compile_without_scratch():
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
     import vmcnt_check
-    vmcnt_check.build_isa()
-    txt = open(os.path.join(vmcnt_check.ISA_DIR, "roi_crop.s")).read()
-    seg = {m.group(1): int(m.group(2)) for m in re.finditer(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)", txt)}
+    seg, lds, txt = vmcnt_check.kernel_segments("roi_crop")
     names = [k for k in seg if "roi_" in k]
     assert len(names) == 5, seg                                    # select; crop: int8 / float32 output, vector / byte stores
     assert sum("roi_select_kernel" in k for k in names) == 1 and sum("roi_crop_kernel" in k for k in names) == 4

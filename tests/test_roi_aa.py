@@ -272,11 +272,8 @@ def test_cropper_antialias_switch(host_net):
 
 def test_roi_crop_aa_kernels_use_no_private_segment_and_bounded_lds():
     import vmcnt_check
-    vmcnt_check.build_isa()
-    txt = open(os.path.join(vmcnt_check.ISA_DIR, "roi_crop_aa.s")).read()
-    seg = {m.group(1): int(m.group(2)) for m in re.finditer(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)", txt)}
-    names = [k for k in seg if "roi_crop_aa_kernel" in k]
+    seg, lds, txt = vmcnt_check.kernel_segments("roi_crop_aa")
+    names = [k for k in seg if "aa_tile_kernel" in k]
     assert len(names) == 2, seg                                    # int8 / float32 output
     assert all(seg[k] == 0 for k in names), seg
-    lds = [int(v) for v in re.findall(r"\.group_segment_fixed_size:\s+(\d+)", txt)]
     assert lds and max(lds) <= 16384, lds                          # bounded whatever the scale: coefficients 40 x 65, two chunks

@@ -173,9 +173,7 @@ def test_ssd_detect_kernels_compile_without_scratch():
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
     import vmcnt_check
-    vmcnt_check.build_isa()
-    txt = open(os.path.join(vmcnt_check.ISA_DIR, "ssd_detect.s")).read()
-    seg = {m.group(1): int(m.group(2)) for m in re.finditer(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)", txt)}
+    seg, lds, txt = vmcnt_check.kernel_segments("ssd_detect")
     names = [k for k in seg if "ssd_" in k]
     assert {"heads", "select", "transpose"} <= {n.split("ssd_")[1].split("_kernel")[0] for n in names}, seg
     assert all(seg[k] == 0 for k in names), seg

@@ -84,12 +84,7 @@ def test_the_two_block_per_cu_bottleneck_kernels_compile_without_scratch(isa_fil
     by which its WRITE_SIZE exceeded its output; without them +0.9 % and +1.0-1.6 % img/s with batches in flight (profiles/r06_experiments.txt item 18).
     The compiled listing of the shipped sources with the shipped flags: conv_bfirst (both instantiations) and the 64-channel shapes of conv_bneck
     (the ones ResNet-50 launches) stay at a private segment of 0 (one shape: three registers)."""
-    isa_dir = os.path.dirname(isa_files[0])
-    seg = {}
-    for src in ("conv_bfirst", "conv_bneck"):
-        txt = open(os.path.join(isa_dir, src + ".s")).read()
-        for m in re.finditer(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)", txt):
-            seg[m.group(1)] = int(m.group(2))
+    seg = {**vmcnt_check.kernel_segments("conv_bfirst")[0], **vmcnt_check.kernel_segments("conv_bneck")[0]}
     bfirst = {k: v for k, v in seg.items() if "conv_bfirst_kernel" in k}
     assert len(bfirst) == 2 and all(v == 0 for v in bfirst.values()), bfirst
     bneck64 = {k: v for k, v in seg.items() if "conv_bneck_kernelILi2ELi4ELi2E" in k}
@@ -99,8 +94,7 @@ def test_the_two_block_per_cu_bottleneck_kernels_compile_without_scratch(isa_fil
 def test_the_short_k_pointwise_kernel_compiles_without_scratch(isa_files):
     """conv_pwk.hip: every instantiation (2 / 4 K slabs x 2 / 4 channel groups, 8 slabs x 4; one / two windows; single and pair launches) at a private segment of 0 -- its first forms
     (eight waves at 128 registers beside up to 64 resident fragment registers) parked 160-470 bytes per lane; four waves per block at <= 256 registers."""
-    txt = open(os.path.join(os.path.dirname(isa_files[0]), "conv_pwk.s")).read()
-    seg = {m.group(1): int(m.group(2)) for m in re.finditer(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)", txt)}
+    seg, _, txt = vmcnt_check.kernel_segments("conv_pwk")
     mine = {k: v for k, v in seg.items() if "conv_pwk_" in k}
     assert len(mine) == 20, mine                                  # (2 / 4 slabs x 2 / 4 channel groups + 8 slabs x 4) x one / two windows, single and pair launches
     assert all(v == 0 for v in mine.values()), mine           # (the two-window K = 512 ones take 293 registers: one block per CU, launch bounds (256, 1))

@@ -284,9 +284,7 @@ def test_the_limits_of_the_desc_pass_every_check():
 
 def test_ycc_kernels_compile_without_scratch():
     import vmcnt_check
-    vmcnt_check.build_isa()
-    txt = open(os.path.join(vmcnt_check.ISA_DIR, "ycc_convert.s")).read()
-    seg = {m.group(1): int(m.group(2)) for m in re.finditer(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)", txt)}
+    seg, lds, txt = vmcnt_check.kernel_segments("ycc_convert")
     names = [k for k in seg if "ycc_to_rgb_kernel" in k]
     assert len(names) == 8, seg                                    # 3- and 4-byte pixels x grey, point, h2v1, h2v2 chroma
     assert all(seg[k] == 0 for k in names), seg

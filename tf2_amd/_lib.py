@@ -413,3 +413,15 @@ def set_opts(**kw) -> None:
 def check(status: int) -> None:
     if status != 0:
         raise Tf2Error(status, lib().tf2_last_error().decode("utf-8", "replace"))
+
+
+def expect(t, dtype, shape=None, device=None, cols=None, ndim=None):
+    """A device tensor an entry point is about to hand to the library: `dtype`, contiguous, on `device` (None: any GPU -- the call's
+    first tensor, whose device the others are held to), with exactly `shape`, or two-dimensional with `cols` columns, or of `ndim`
+    dimensions.  AssertionError naming what it got; returns the tensor's device."""
+    ok = t.dtype == dtype and t.is_contiguous() and (t.device.type == "cuda" if device is None else t.device == device)
+    ok = ok and (shape is None or tuple(t.shape) == tuple(shape)) and (cols is None or (t.dim() == 2 and t.shape[1] == cols))
+    want = tuple(shape) if shape is not None else f"[n, {cols}]" if cols is not None else f"{ndim}-d" if ndim is not None else ""
+    assert ok and (ndim is None or t.dim() == ndim), f"expected {dtype} {want} contiguous on {device or 'a GPU'}, got {t.dtype} " \
+        f"{tuple(t.shape)} on {t.device}{'' if t.is_contiguous() else ', not contiguous'}"
+    return t.device

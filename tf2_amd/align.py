@@ -265,18 +265,17 @@ class DeviceAligner:
     def fit(self, rois, lmk, stream=None, xforms=None, status=None):
         import torch
         from . import _lib
-        dev = rois.device
-        assert rois.dtype == torch.int32 and rois.is_contiguous() and dev.type == "cuda" and rois.dim() == 2 and rois.shape[1] == R.ROI_WORDS
+        dev = _lib.expect(rois, torch.int32, cols=R.ROI_WORDS)
         S = rois.shape[0]
-        assert lmk.dtype == torch.float32 and lmk.is_contiguous() and lmk.device == dev and tuple(lmk.shape) == (S, self.n_points, 2), tuple(lmk.shape)
+        _lib.expect(lmk, torch.float32, (S, self.n_points, 2), dev)
         stream = stream or torch.cuda.current_stream(dev)
         with torch.cuda.stream(stream):
             if xforms is None:
                 xforms = torch.empty(S, XFORM_WORDS, dtype=torch.int32, device=dev)
             if status is None:
                 status = torch.empty(S, dtype=torch.int32, device=dev)
-            assert xforms.dtype == torch.int32 and xforms.is_contiguous() and xforms.device == dev and tuple(xforms.shape) == (S, XFORM_WORDS)
-            assert status.dtype == torch.int32 and status.is_contiguous() and status.device == dev and tuple(status.shape) == (S,)
+            _lib.expect(xforms, torch.int32, (S, XFORM_WORDS), dev)
+            _lib.expect(status, torch.int32, (S,), dev)
             _lib.check(_lib.lib().tf2_roi_fit(C.byref(self.fit_desc), rois.data_ptr(), lmk.data_ptr(), S, xforms.data_ptr(),
                                               status.data_ptr(), stream.cuda_stream))
         return xforms, status
@@ -285,20 +284,11 @@ class DeviceAligner:
         import torch
         from . import _lib
         assert out in ("q", "f32"), out
-        dev = pixels.device
-        assert pixels.dtype == torch.uint8 and pixels.is_contiguous() and dev.type == "cuda"
-        assert srcs.dtype == torch.int32 and srcs.is_contiguous() and srcs.device == dev and srcs.dim() == 2 and srcs.shape[1] == P.SRC_WORDS
-        assert xforms.dtype == torch.int32 and xforms.is_contiguous() and xforms.device == dev and xforms.dim() == 2 and xforms.shape[1] == XFORM_WORDS
+        dev = _lib.expect(pixels, torch.uint8)
+        _lib.expect(srcs, torch.int32, device=dev, cols=P.SRC_WORDS)
+        _lib.expect(xforms, torch.int32, device=dev, cols=XFORM_WORDS)
         B, S = srcs.shape[0], xforms.shape[0]
-        dtype = torch.int8 if out == "q" else torch.float32
-        stream = stream or torch.cuda.current_stream(dev)
-        with torch.cuda.stream(stream):
-            if images is None:
-                images = torch.empty(S, 3, *self.out_hw, dtype=dtype, device=dev)
-            if status is None:
-                status = torch.empty(S, dtype=torch.int32, device=dev)
-            assert images.dtype == dtype and images.is_contiguous() and images.device == dev and tuple(images.shape) == (S, 3) + self.out_hw
-            assert status.dtype == torch.int32 and status.is_contiguous() and status.device == dev and tuple(status.shape) == (S,)
+        with P.image_outputs(out, S, self.out_hw, dev, stream, images, status) as (images, status, stream):
             _lib.check(_lib.lib().tf2_roi_warp(self.net._h, C.byref(self.desc), pixels.data_ptr(), pixels.numel(), srcs.data_ptr(), B,
                                                xforms.data_ptr(), S, int(out == "q"), images.data_ptr(), status.data_ptr(),
                                                stream.cuda_stream))

@@ -324,7 +324,7 @@ tf2_status Auditor::create(Net* n) {
 size_t Auditor::workspace_size(int batch) { return batch <= 0 ? 0 : net->workspace_size(batch, true); }
 
 tf2_status Auditor::store_init(void* store, size_t store_bytes, void* stream) const {
-  if (!store) { set_error("tf2_audit_store_init: null store_dev"); return TF2_ERR_ARG; }
+  if (!store) return arg_refusal("tf2_audit_store_init", "null store_dev");
   if (store_bytes < store_size()) { set_error("tf2_audit_store_init: store too small (tf2_audit_store_size: " + std::to_string(store_size()) + ")"); return TF2_ERR_SIZE; }
   if (launch_audit_init((long long*)store, n_records, stream)) { set_error(std::string("tf2_audit_store_init: launch failed: ") + hipGetErrorString(hipGetLastError())); return TF2_ERR_HIP; }
   return TF2_OK;
@@ -333,8 +333,8 @@ tf2_status Auditor::store_init(void* store, size_t store_bytes, void* stream) co
 // with_step: the keep_all step first (tf2_audit_run); without, the audit alone of a workspace that holds one (tf2_audit_kept)
 tf2_status Auditor::run(const void* images, bool images_are_q, int batch, void* ws, size_t ws_bytes, int8_t* logits, void* store,
                         size_t store_bytes, void* stream, bool with_step) {
-  if (batch <= 0) { set_error("tf2_audit_run: batch must be positive"); return TF2_ERR_ARG; }
-  if (!images || !ws || (with_step && !logits) || !store) { set_error("tf2_audit_run: null device pointer"); return TF2_ERR_ARG; }
+  if (batch <= 0) return arg_refusal("tf2_audit_run", "batch must be positive");
+  if (!images || !ws || (with_step && !logits) || !store) return arg_refusal("tf2_audit_run", "null device pointer");
   if (!net->packed_valid) { set_error("tf2_audit_run: no packed image (tf2_net_pack / tf2_net_packed_adopt)"); return TF2_ERR_STATE; }
   if (!net->packed_dev) { set_error("tf2_audit_run: packed image not bound to the device (tf2_net_bind_device)"); return TF2_ERR_STATE; }
   if ((int)rows.size() != net->nd.n_layers + 1) { set_error("tf2_audit_run: the handle does not fit the net"); return TF2_ERR_STATE; }

@@ -265,8 +265,8 @@ __global__ __launch_bounds__(kThreads) void caq_error_kernel(CaqArgs p) {
 }  // namespace
 
 tf2_status caq_store_init(void* store, size_t store_bytes, void* stream) {
-  if (!store) { set_error("tf2_caq_store_init: null store_dev"); return TF2_ERR_ARG; }
-  if (store_bytes == 0 || store_bytes % 8 != 0 || ((uintptr_t)store & 7) != 0) { set_error("tf2_caq_store_init: the store is whole, 8-byte aligned int64 words"); return TF2_ERR_ARG; }
+  if (!store) return arg_refusal("tf2_caq_store_init", "null store_dev");
+  if (store_bytes == 0 || store_bytes % 8 != 0 || ((uintptr_t)store & 7) != 0) return arg_refusal("tf2_caq_store_init", "the store is whole, 8-byte aligned int64 words");
   if (hipMemsetAsync(store, 0, store_bytes, (hipStream_t)stream) != hipSuccess) { set_error(std::string("tf2_caq_store_init: memset failed: ") + hipGetErrorString(hipGetLastError())); return TF2_ERR_HIP; }
   return TF2_OK;
 }

@@ -316,7 +316,7 @@ tf2_status Comparator::create(Net* n) {
 }
 
 tf2_status Comparator::store_init(void* store, size_t store_bytes, void* stream) const {
-  if (!store) { set_error("tf2_fid_store_init: null store_dev"); return TF2_ERR_ARG; }
+  if (!store) return arg_refusal("tf2_fid_store_init", "null store_dev");
   if (store_bytes < store_size()) { set_error("tf2_fid_store_init: store too small (tf2_fid_store_size: " + std::to_string(store_size()) + ")"); return TF2_ERR_SIZE; }
   if (hipMemsetAsync(store, 0, store_size(), (hipStream_t)stream) != hipSuccess) { set_error(std::string("tf2_fid_store_init: memset failed: ") + hipGetErrorString(hipGetLastError())); return TF2_ERR_HIP; }
   return TF2_OK;
@@ -325,8 +325,8 @@ tf2_status Comparator::store_init(void* store, size_t store_bytes, void* stream)
 // with_step: the keep_all step first (tf2_fid_run); without, the comparison alone of a workspace that holds one (tf2_fid_kept)
 tf2_status Comparator::run(const void* images, bool images_are_q, int batch, void* ws, size_t ws_bytes, int8_t* logits, void* store,
                            size_t store_bytes, const float* const* refs, const float* scales_dev, void* stream, bool with_step) {
-  if (batch <= 0) { set_error("tf2_fid_run: batch must be positive"); return TF2_ERR_ARG; }
-  if (!images || !ws || (with_step && !logits) || !store || !refs || !scales_dev) { set_error("tf2_fid_run: null pointer"); return TF2_ERR_ARG; }
+  if (batch <= 0) return arg_refusal("tf2_fid_run", "batch must be positive");
+  if (!images || !ws || (with_step && !logits) || !store || !refs || !scales_dev) return arg_refusal("tf2_fid_run", "null pointer");
   if (!net->packed_valid) { set_error("tf2_fid_run: no packed image (tf2_net_pack / tf2_net_packed_adopt)"); return TF2_ERR_STATE; }
   if (!net->packed_dev) { set_error("tf2_fid_run: packed image not bound to the device (tf2_net_bind_device)"); return TF2_ERR_STATE; }
   if ((int)aud.rows.size() != net->nd.n_layers + 1) { set_error("tf2_fid_run: the handle does not fit the net"); return TF2_ERR_STATE; }

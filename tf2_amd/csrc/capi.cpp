@@ -62,7 +62,7 @@ int tf2_check_dma_errors(unsigned long long out[2]) {
 uint8_t tf2_get_real(float w, int8_t expand) { return get_real(w, expand); }
 
 tf2_status tf2_net_create(const tf2_net_desc* nd, const tf2_layer_desc* layers, tf2_net** out) {
-  if (!nd || !layers || !out) { set_error("tf2_net_create: null argument"); return TF2_ERR_ARG; }
+  if (!nd || !layers || !out) return arg_refusal("tf2_net_create", "null argument");
   // the option snapshot (TF2_AMD_OPTS, opts.h) is taken here and by tf2_net_reload_options, nowhere else
   { const std::string e = opts_reload(); if (!e.empty()) { set_error(e); return TF2_ERR_ARG; } }
   tf2_net* n = new (std::nothrow) tf2_net();
@@ -83,7 +83,7 @@ void tf2_net_destroy(tf2_net* net) {
 tf2_status tf2_quantization(const tf2_net* net, const char* q_text, size_t q_text_len, int8_t* q,
                             size_t q_capacity, int32_t* n_values_read) {
   CHECK_NET(net);
-  if (!q_text || !q) { set_error("tf2_quantization: null argument"); return TF2_ERR_ARG; }
+  if (!q_text || !q) return arg_refusal("tf2_quantization", "null argument");
   return net->impl.quantization(q_text, q_text_len, q, q_capacity, n_values_read);
 }
 
@@ -100,12 +100,12 @@ tf2_status tf2_net_set_q(tf2_net* net, const int8_t* q, size_t n_bytes) {
 
 tf2_status tf2_net_load_model(tf2_net* net, const float* model, size_t n_floats) {
   CHECK_NET(net);
-  if (!model) { set_error("tf2_net_load_model: null model"); return TF2_ERR_ARG; }
+  if (!model) return arg_refusal("tf2_net_load_model", "null model");
   return net->impl.load_model(model, n_floats);
 }
 
 tf2_status tf2_model4bit_decode(const void* bytes, size_t n_bytes, float* floats, size_t capacity, size_t* n_floats) {
-  if (!bytes) { set_error("tf2_model4bit_decode: null input"); return TF2_ERR_ARG; }
+  if (!bytes) return arg_refusal("tf2_model4bit_decode", "null input");
   std::vector<float> out;
   size_t cnt = 0;
   const std::string err = tf2::model4bit_decode((const uint8_t*)bytes, n_bytes, floats ? &out : nullptr, &cnt);
@@ -120,7 +120,7 @@ tf2_status tf2_model4bit_decode(const void* bytes, size_t n_bytes, float* floats
 
 tf2_status tf2_net_load_model_4bit(tf2_net* net, const void* bytes, size_t n_bytes) {
   CHECK_NET(net);
-  if (!bytes) { set_error("tf2_net_load_model_4bit: null input"); return TF2_ERR_ARG; }
+  if (!bytes) return arg_refusal("tf2_net_load_model_4bit", "null input");
   return net->impl.load_model_4bit((const uint8_t*)bytes, n_bytes);
 }
 
@@ -167,9 +167,9 @@ tf2_status tf2_net_packed_adopt(tf2_net* net, const void* host_src, size_t n_byt
   if (!host_src || n_bytes < sizeof(PackHeader)) { set_error("tf2_net_packed_adopt: image too small"); return TF2_ERR_SIZE; }
   PackHeader h;
   std::memcpy(&h, host_src, sizeof h);
-  if (h.magic != kPackMagic || h.version != kPackVersion) { set_error("tf2_net_packed_adopt: not a tf2_amd packed image of this version"); return TF2_ERR_ARG; }
+  if (h.magic != kPackMagic || h.version != kPackVersion) return arg_refusal("tf2_net_packed_adopt", "not a tf2_amd packed image of this version");
   if (h.total_bytes != n_bytes || h.n_layers != (uint32_t)N.nd.n_layers) { set_error("tf2_net_packed_adopt: size / layer count mismatch"); return TF2_ERR_SIZE; }
-  if (h.tables_hash != N.tables_hash()) { set_error("tf2_net_packed_adopt: image was packed for different network tables"); return TF2_ERR_ARG; }
+  if (h.tables_hash != N.tables_hash()) return arg_refusal("tf2_net_packed_adopt", "image was packed for different network tables");
   N.packed.assign((const uint8_t*)host_src, (const uint8_t*)host_src + n_bytes);
   N.packed_valid = true;
   N.packed_dev = nullptr; N.packed_dev_bytes = 0;
@@ -208,23 +208,23 @@ tf2_status tf2_net_reload_options(tf2_net* net) {
 tf2_status tf2_net_run(tf2_net* net, const float* images_dev, int batch, void* ws, size_t ws_bytes,
                        int8_t* logits_dev, void* hip_stream) {
   CHECK_NET(net);
-  if (!images_dev || !ws) { set_error("tf2_net_run: null device pointer"); return TF2_ERR_ARG; }
+  if (!images_dev || !ws) return arg_refusal("tf2_net_run", "null device pointer");
   return net->impl.run(images_dev, false, batch, ws, ws_bytes, logits_dev, hip_stream);
 }
 
 tf2_status tf2_net_run_q(tf2_net* net, const int8_t* images_q_dev, int batch, void* ws, size_t ws_bytes,
                          int8_t* logits_dev, void* hip_stream) {
   CHECK_NET(net);
-  if (!images_q_dev || !ws) { set_error("tf2_net_run_q: null device pointer"); return TF2_ERR_ARG; }
+  if (!images_q_dev || !ws) return arg_refusal("tf2_net_run_q", "null device pointer");
   return net->impl.run(images_q_dev, true, batch, ws, ws_bytes, logits_dev, hip_stream);
 }
 
 tf2_status tf2_net_run_ex(tf2_net* net, const void* images_dev, int batch, void* ws, size_t ws_bytes, int8_t* logits_dev,
                           void* hip_stream, const tf2_run_opts* o) {
   CHECK_NET(net);
-  if (!images_dev || !ws) { set_error("tf2_net_run_ex: null device pointer"); return TF2_ERR_ARG; }
-  if (!o || o->size < sizeof(tf2_run_opts)) { set_error("tf2_net_run_ex: opts missing or older than this library's tf2_run_opts"); return TF2_ERR_ARG; }
-  if (o->concurrency < -1 || o->concurrency > 1) { set_error("tf2_net_run_ex: concurrency must be -1, 0 or 1"); return TF2_ERR_ARG; }
+  if (!images_dev || !ws) return arg_refusal("tf2_net_run_ex", "null device pointer");
+  if (!o || o->size < sizeof(tf2_run_opts)) return arg_refusal("tf2_net_run_ex", "opts missing or older than this library's tf2_run_opts");
+  if (o->concurrency < -1 || o->concurrency > 1) return arg_refusal("tf2_net_run_ex", "concurrency must be -1, 0 or 1");
   if (o->mark_event && (o->mark_after_layer < 0 || o->mark_after_layer >= net->impl.nd.n_layers)) {
     set_error("tf2_net_run_ex: mark_after_layer outside the layer table"); return TF2_ERR_ARG;
   }
@@ -233,7 +233,7 @@ tf2_status tf2_net_run_ex(tf2_net* net, const void* images_dev, int batch, void*
 
 tf2_status tf2_net_run_stats(tf2_net* net, int64_t* out4) {
   CHECK_NET(net);
-  if (!out4) { set_error("tf2_net_run_stats: null argument"); return TF2_ERR_ARG; }
+  if (!out4) return arg_refusal("tf2_net_run_stats", "null argument");
   std::lock_guard<std::mutex> lock(net->impl.run_mutex);
   out4[0] = net->impl.stat_steps; out4[1] = net->impl.stat_group_steps; out4[2] = net->impl.stat_inflight_steps; out4[3] = net->impl.stat_small_mask_steps;
   return TF2_OK;
@@ -247,7 +247,7 @@ tf2_status tf2_net_poll_error(tf2_net* net, int batch, void* workspace, size_t w
 
 tf2_status tf2_net_describe_launches(tf2_net* net, int batch, int concurrency, tf2_launch_info* rows, int capacity, int* n) {
   CHECK_NET(net);
-  if (!n || (capacity > 0 && !rows)) { set_error("tf2_net_describe_launches: null argument"); return TF2_ERR_ARG; }
+  if (!n || (capacity > 0 && !rows)) return arg_refusal("tf2_net_describe_launches", "null argument");
   std::vector<std::pair<int, LaunchRecord>> v;
   tf2_status st = net->impl.describe_launches(batch, concurrency != 0, &v);
   if (st != TF2_OK) return st;
@@ -265,7 +265,7 @@ tf2_status tf2_net_describe_launches(tf2_net* net, int batch, int concurrency, t
 tf2_status tf2_net_describe_workspace(tf2_net* net, int batch, int keep_all, tf2_tensor_info* tensors, int tensor_capacity, int* n_tensors,
                                       tf2_row_tensors* rows, int row_capacity) {
   CHECK_NET(net);
-  if (!n_tensors || (tensor_capacity > 0 && !tensors) || (row_capacity > 0 && !rows)) { set_error("tf2_net_describe_workspace: null argument"); return TF2_ERR_ARG; }
+  if (!n_tensors || (tensor_capacity > 0 && !tensors) || (row_capacity > 0 && !rows)) return arg_refusal("tf2_net_describe_workspace", "null argument");
   std::vector<tf2::TensorPlan> t;
   std::vector<tf2::LayerExec> r;
   tf2_status st = net->impl.describe_workspace(batch, keep_all != 0, &t, &r);
@@ -284,7 +284,7 @@ tf2_status tf2_net_describe_workspace(tf2_net* net, int batch, int keep_all, tf2
 
 tf2_status tf2_ssd_create(tf2_net* net, const tf2_ssd_desc* d, tf2_ssd** out) {
   CHECK_NET(net);
-  if (!d || !out) { set_error("tf2_ssd_create: null argument"); return TF2_ERR_ARG; }
+  if (!d || !out) return arg_refusal("tf2_ssd_create", "null argument");
   tf2_ssd* s = new (std::nothrow) tf2_ssd();
   if (!s) { set_error("out of memory"); return TF2_ERR_SIZE; }
   const tf2_status st = s->impl.create(&net->impl, d);
@@ -380,7 +380,7 @@ tf2_status tf2_jpeg_huff(const tf2_jpeg_huff_desc* d, const uint8_t* bytes_dev, 
 
 tf2_status tf2_cls_create(tf2_net* net, const tf2_cls_desc* d, tf2_cls** out) {
   CHECK_NET(net);
-  if (!out) { set_error("tf2_cls_create: null argument"); return TF2_ERR_ARG; }
+  if (!out) return arg_refusal("tf2_cls_create", "null argument");
   tf2_cls* c = new (std::nothrow) tf2_cls();
   if (!c) { set_error("out of memory"); return TF2_ERR_SIZE; }
   const tf2_status st = c->impl.create(&net->impl, d);
@@ -393,15 +393,15 @@ void tf2_cls_destroy(tf2_cls* c) { delete c; }
 
 tf2_status tf2_cls_run(tf2_cls* c, const int8_t* logits_dev, int batch, int32_t* labels_dev, float* features_dev, float* probs_dev,
                        float* all_probs_dev, const int32_t* truth_dev, int32_t* rank_dev, uint64_t* tally_dev, void* stream) {
-  if (batch < 1) { set_error("tf2_cls_run: batch must be >= 1"); return TF2_ERR_ARG; }
-  if (!logits_dev || !labels_dev) { set_error("tf2_cls_run: null logits_dev / labels_dev"); return TF2_ERR_ARG; }
+  if (batch < 1) return arg_refusal("tf2_cls_run", "batch must be >= 1");
+  if (!logits_dev || !labels_dev) return arg_refusal("tf2_cls_run", "null logits_dev / labels_dev");
   if (!c) { set_error("null tf2_cls handle"); return TF2_ERR_ARG; }
   return c->impl.run(logits_dev, batch, labels_dev, features_dev, probs_dev, all_probs_dev, truth_dev, rank_dev, tally_dev, stream);
 }
 
 tf2_status tf2_emb_create(tf2_net* net, const tf2_emb_desc* d, tf2_emb** out) {
   CHECK_NET(net);
-  if (!out) { set_error("tf2_emb_create: null argument"); return TF2_ERR_ARG; }
+  if (!out) return arg_refusal("tf2_emb_create", "null argument");
   tf2_emb* m = new (std::nothrow) tf2_emb();
   if (!m) { set_error("out of memory"); return TF2_ERR_SIZE; }
   const tf2_status st = m->impl.create(&net->impl, d);
@@ -415,8 +415,8 @@ void tf2_emb_destroy(tf2_emb* m) { delete m; }
 size_t tf2_emb_scratch_size(const tf2_emb* m, int batch, int n_rows) { return m ? m->impl.scratch_size(batch, n_rows) : 0; }
 
 tf2_status tf2_emb_embed(tf2_emb* m, const int8_t* out_i8_dev, int batch, float* rows_dev, void* stream) {
-  if (batch < 1) { set_error("tf2_emb_embed: batch must be >= 1"); return TF2_ERR_ARG; }
-  if (!out_i8_dev || !rows_dev) { set_error("tf2_emb_embed: null out_i8_dev / rows_dev"); return TF2_ERR_ARG; }
+  if (batch < 1) return arg_refusal("tf2_emb_embed", "batch must be >= 1");
+  if (!out_i8_dev || !rows_dev) return arg_refusal("tf2_emb_embed", "null out_i8_dev / rows_dev");
   if (!m) { set_error("null tf2_emb handle"); return TF2_ERR_ARG; }
   return m->impl.embed(out_i8_dev, batch, rows_dev, stream);
 }
@@ -424,12 +424,12 @@ tf2_status tf2_emb_embed(tf2_emb* m, const int8_t* out_i8_dev, int batch, float*
 tf2_status tf2_emb_match(tf2_emb* m, const int8_t* out_i8_dev, int batch, const float* gallery_dev, const int32_t* gallery_ids_dev,
                          int n_rows, float threshold, void* scratch_dev, size_t scratch_bytes, int32_t* idx_dev, float* dist_dev,
                          int32_t* ids_out_dev, float* emb_out_dev, const int32_t* truth_dev, uint64_t* tally_dev, void* stream) {
-  if (batch < 1) { set_error("tf2_emb_match: batch must be >= 1"); return TF2_ERR_ARG; }
-  if (n_rows < 1) { set_error("tf2_emb_match: n_rows must be >= 1"); return TF2_ERR_ARG; }
-  if (!out_i8_dev || !gallery_dev) { set_error("tf2_emb_match: null out_i8_dev / gallery_dev"); return TF2_ERR_ARG; }
-  if (!scratch_dev) { set_error("tf2_emb_match: null scratch_dev"); return TF2_ERR_ARG; }
-  if (!idx_dev || !dist_dev) { set_error("tf2_emb_match: null idx_dev / dist_dev"); return TF2_ERR_ARG; }
-  if (threshold != threshold) { set_error("tf2_emb_match: threshold is NaN"); return TF2_ERR_ARG; }
+  if (batch < 1) return arg_refusal("tf2_emb_match", "batch must be >= 1");
+  if (n_rows < 1) return arg_refusal("tf2_emb_match", "n_rows must be >= 1");
+  if (!out_i8_dev || !gallery_dev) return arg_refusal("tf2_emb_match", "null out_i8_dev / gallery_dev");
+  if (!scratch_dev) return arg_refusal("tf2_emb_match", "null scratch_dev");
+  if (!idx_dev || !dist_dev) return arg_refusal("tf2_emb_match", "null idx_dev / dist_dev");
+  if (threshold != threshold) return arg_refusal("tf2_emb_match", "threshold is NaN");
   if (!m) { set_error("null tf2_emb handle"); return TF2_ERR_ARG; }
   return m->impl.match(out_i8_dev, batch, gallery_dev, gallery_ids_dev, n_rows, threshold, scratch_dev, scratch_bytes, idx_dev, dist_dev,
                        ids_out_dev, emb_out_dev, truth_dev, tally_dev, stream);
@@ -447,7 +447,7 @@ tf2_status tf2_emb_roc_pairs(const float* rows_dev, int n_rows, int d, const int
 
 tf2_status tf2_audit_create(tf2_net* net, tf2_audit** out) {
   CHECK_NET(net);
-  if (!out) { set_error("tf2_audit_create: null argument"); return TF2_ERR_ARG; }
+  if (!out) return arg_refusal("tf2_audit_create", "null argument");
   tf2_audit* a = new (std::nothrow) tf2_audit();
   if (!a) { set_error("out of memory"); return TF2_ERR_SIZE; }
   const tf2_status st = a->impl.create(&net->impl);
@@ -462,7 +462,7 @@ size_t tf2_audit_store_size(const tf2_audit* a) { return a ? a->impl.store_size(
 
 tf2_status tf2_audit_describe(const tf2_audit* a, tf2_audit_row* rows, int capacity, int* n) {
   if (!a) { set_error("null tf2_audit handle"); return TF2_ERR_ARG; }
-  if (!n || (capacity > 0 && !rows)) { set_error("tf2_audit_describe: null argument"); return TF2_ERR_ARG; }
+  if (!n || (capacity > 0 && !rows)) return arg_refusal("tf2_audit_describe", "null argument");
   const auto& v = a->impl.rows;
   *n = (int)v.size();
   if ((int)v.size() > capacity) { set_error("tf2_audit_describe: " + std::to_string(v.size()) + " rows, capacity " + std::to_string(capacity)); return TF2_ERR_SIZE; }
@@ -495,7 +495,7 @@ tf2_status tf2_audit_kept(tf2_audit* a, const void* images_dev, int images_are_q
 
 tf2_status tf2_fid_create(tf2_net* net, tf2_fid** out) {
   CHECK_NET(net);
-  if (!out) { set_error("tf2_fid_create: null argument"); return TF2_ERR_ARG; }
+  if (!out) return arg_refusal("tf2_fid_create", "null argument");
   tf2_fid* f = new (std::nothrow) tf2_fid();
   if (!f) { set_error("out of memory"); return TF2_ERR_SIZE; }
   const tf2_status st = f->impl.create(&net->impl);
@@ -510,7 +510,7 @@ size_t tf2_fid_store_size(const tf2_fid* f) { return f ? f->impl.store_size() : 
 
 tf2_status tf2_fid_describe(const tf2_fid* f, tf2_audit_row* rows, int capacity, int* n) {
   if (!f) { set_error("null tf2_fid handle"); return TF2_ERR_ARG; }
-  if (!n || (capacity > 0 && !rows)) { set_error("tf2_fid_describe: null argument"); return TF2_ERR_ARG; }
+  if (!n || (capacity > 0 && !rows)) return arg_refusal("tf2_fid_describe", "null argument");
   const auto& v = f->impl.aud.rows;
   *n = (int)v.size();
   if ((int)v.size() > capacity) { set_error("tf2_fid_describe: " + std::to_string(v.size()) + " rows, capacity " + std::to_string(capacity)); return TF2_ERR_SIZE; }
@@ -524,7 +524,7 @@ tf2_status tf2_fid_describe(const tf2_fid* f, tf2_audit_row* rows, int capacity,
 
 tf2_status tf2_fid_scales(const tf2_fid* f, float* scales, int capacity, int* n) {
   if (!f) { set_error("null tf2_fid handle"); return TF2_ERR_ARG; }
-  if (!n || (capacity > 0 && !scales)) { set_error("tf2_fid_scales: null argument"); return TF2_ERR_ARG; }
+  if (!n || (capacity > 0 && !scales)) return arg_refusal("tf2_fid_scales", "null argument");
   const auto& v = f->impl.scale;
   *n = (int)v.size();
   if ((int)v.size() > capacity) { set_error("tf2_fid_scales: " + std::to_string(v.size()) + " records, capacity " + std::to_string(capacity)); return TF2_ERR_SIZE; }
@@ -600,7 +600,7 @@ tf2_status tf2_inq_step(float* weights_dev, uint8_t* mask_dev, int64_t n_total, 
 }
 
 tf2_status tf2_det_eval_create(const tf2_det_eval_desc* d, tf2_det_eval** out) {
-  if (!out) { set_error("tf2_det_eval_create: null argument"); return TF2_ERR_ARG; }
+  if (!out) return arg_refusal("tf2_det_eval_create", "null argument");
   tf2_det_eval* e = new (std::nothrow) tf2_det_eval();
   if (!e) { set_error("out of memory"); return TF2_ERR_SIZE; }
   const tf2_status st = e->impl.create(d);
@@ -621,10 +621,10 @@ tf2_status tf2_det_eval_store_init(const tf2_det_eval* e, void* store_dev, size_
 tf2_status tf2_det_eval_run(const tf2_det_eval* e, const float* det_dev, const int32_t* counts_dev, const tf2_gt_box* gt_dev,
                             const int32_t* gt_count_dev, const int32_t* slot_dev, int batch, void* store_dev, size_t store_bytes,
                             int32_t* status_dev, int8_t* flags_out_dev, void* hip_stream) {
-  if (batch < 1) { set_error("tf2_det_eval_run: batch must be >= 1"); return TF2_ERR_ARG; }
-  if (!det_dev || !counts_dev) { set_error("tf2_det_eval_run: null det_dev / counts_dev"); return TF2_ERR_ARG; }
-  if (!gt_dev || !gt_count_dev || !slot_dev) { set_error("tf2_det_eval_run: null gt_dev / gt_count_dev / slot_dev"); return TF2_ERR_ARG; }
-  if (!store_dev || !status_dev) { set_error("tf2_det_eval_run: null store_dev / status_dev"); return TF2_ERR_ARG; }
+  if (batch < 1) return arg_refusal("tf2_det_eval_run", "batch must be >= 1");
+  if (!det_dev || !counts_dev) return arg_refusal("tf2_det_eval_run", "null det_dev / counts_dev");
+  if (!gt_dev || !gt_count_dev || !slot_dev) return arg_refusal("tf2_det_eval_run", "null gt_dev / gt_count_dev / slot_dev");
+  if (!store_dev || !status_dev) return arg_refusal("tf2_det_eval_run", "null store_dev / status_dev");
   if (!e) { set_error("null tf2_det_eval handle"); return TF2_ERR_ARG; }
   return e->impl.run(det_dev, counts_dev, gt_dev, gt_count_dev, slot_dev, batch, store_dev, store_bytes, status_dev, flags_out_dev, hip_stream);
 }
@@ -638,7 +638,7 @@ tf2_status tf2_det_eval_summarise(const tf2_det_eval* e, const void* store_host,
 tf2_status tf2_net_read_layer(tf2_net* net, int layer, int batch, const void* ws, int8_t* host_dst,
                               size_t capacity, void* hip_stream) {
   CHECK_NET(net);
-  if (!ws || !host_dst) { set_error("tf2_net_read_layer: null pointer"); return TF2_ERR_ARG; }
+  if (!ws || !host_dst) return arg_refusal("tf2_net_read_layer", "null pointer");
   return net->impl.read_layer(layer, batch, ws, host_dst, capacity, hip_stream);
 }
 
@@ -677,12 +677,12 @@ tf2_status tf2_net_profile_loop_read(tf2_net* net, float* ms_total, int32_t* run
 // Evaluation(), network_helper.cpp:143-207: feature = out / (1 << Q); k bubble passes with
 // '>' (ties: the larger index ends up on top).
 tf2_status tf2_topk(const int8_t* logits, const int8_t* q_last_row, int n, int k, int32_t* labels, float* features) {
-  if (!logits || !q_last_row || !labels || n <= 0 || k <= 0 || k > n) { set_error("tf2_topk: bad argument"); return TF2_ERR_ARG; }
+  if (!logits || !q_last_row || !labels || n <= 0 || k <= 0 || k > n) return arg_refusal("tf2_topk", "bad argument");
   std::vector<float> f(n);
   std::vector<int32_t> lab(n);
   for (int i = 0; i < n; i++) {
     const int sh = -(int)q_last_row[i];
-    if (sh < 0 || sh > 30) { set_error("tf2_topk: Q of the last layer must be in 0..30 (network_helper.cpp:181)"); return TF2_ERR_ARG; }
+    if (sh < 0 || sh > 30) return arg_refusal("tf2_topk", "Q of the last layer must be in 0..30 (network_helper.cpp:181)");
     f[i] = (float)logits[i] / (float)(1 << sh);
     lab[i] = i;
   }

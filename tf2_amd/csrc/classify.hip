@@ -145,7 +145,7 @@ Classifier::~Classifier() {
 }
 
 tf2_status Classifier::create(const Net* net, const tf2_cls_desc* d) {
-  auto fail = [](const std::string& m) { set_error("tf2_cls_create: " + m); return TF2_ERR_ARG; };
+  auto fail = [](const std::string& m) { return arg_refusal("tf2_cls_create", m); };
   if (!d || d->size != sizeof(tf2_cls_desc)) return fail("desc size: missing, or not sizeof(tf2_cls_desc)");
   if (net->q.empty()) { set_error("tf2_cls_create: q table not set (tf2_net_set_q first)"); return TF2_ERR_STATE; }
   const tf2_layer_desc& LL = net->layers[net->nd.n_layers - 1];
@@ -183,9 +183,7 @@ tf2_status Classifier::run(const int8_t* logits, int batch, int32_t* labels, flo
   a.n = n; a.top_k = top_k; a.batch = batch;
   const dim3 grid((unsigned)((batch + kClsWaves - 1) / kClsWaves)), block(kClsThreads);
   hipLaunchKernelGGL(classify_kernel, grid, block, (size_t)kClsWaves * n * sizeof(uint32_t), (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("tf2_cls_run: launch failed: ") + hipGetErrorString(e)); return TF2_ERR_HIP; }
-  return TF2_OK;
+  return launch_result("tf2_cls_run");
 }
 
 }  // namespace tf2

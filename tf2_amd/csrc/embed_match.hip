@@ -250,7 +250,7 @@ Matcher::~Matcher() {
 }
 
 tf2_status Matcher::create(const Net* net, const tf2_emb_desc* desc) {
-  auto fail = [](const std::string& m) { set_error("tf2_emb_create: " + m); return TF2_ERR_ARG; };
+  auto fail = [](const std::string& m) { return arg_refusal("tf2_emb_create", m); };
   if (!desc || desc->size != sizeof(tf2_emb_desc)) return fail("desc size: missing, or not sizeof(tf2_emb_desc)");
   if (net->q.empty()) { set_error("tf2_emb_create: q table not set (tf2_net_set_q first)"); return TF2_ERR_STATE; }
   const tf2_layer_desc& LL = net->layers[net->nd.n_layers - 1];
@@ -286,9 +286,7 @@ size_t Matcher::scratch_size(int batch, long long n_rows) const {
 tf2_status Matcher::embed(const int8_t* out_i8, int batch, float* rows, void* stream) {
   const dim3 grid((unsigned)((batch + kWaves - 1) / kWaves)), block(kThreads);
   hipLaunchKernelGGL(embed_kernel, grid, block, 0, (hipStream_t)stream, out_i8, (const float*)consts, rows, (float*)nullptr, d, batch, 0);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("tf2_emb_embed: launch failed: ") + hipGetErrorString(e)); return TF2_ERR_HIP; }
-  return TF2_OK;
+  return launch_result("tf2_emb_embed");
 }
 
 tf2_status Matcher::match(const int8_t* out_i8, int batch, const float* gallery, const int32_t* gallery_ids, long long n_rows,
@@ -300,7 +298,7 @@ tf2_status Matcher::match(const int8_t* out_i8, int batch, const float* gallery,
     set_error("tf2_emb_match: scratch_bytes " + std::to_string(scratch_bytes) + " < tf2_emb_scratch_size " + std::to_string(need));
     return TF2_ERR_SIZE;
   }
-  if (((uintptr_t)scratch & 7) != 0) { set_error("tf2_emb_match: scratch_dev must be 8-byte aligned"); return TF2_ERR_ARG; }
+  if (((uintptr_t)scratch & 7) != 0) return arg_refusal("tf2_emb_match", "scratch_dev must be 8-byte aligned");
   const int bp = padded_batch(batch);
   const long long slabs = slabs_of(n_rows);
   if (slabs > 0x7fffffffll || (long long)bp / kEmbGroup > 65535) { set_error("tf2_emb_match: too many slabs or query groups for one grid"); return TF2_ERR_UNSUPPORTED; }
@@ -317,9 +315,7 @@ tf2_status Matcher::match(const int8_t* out_i8, int batch, const float* gallery,
   a.tally = reinterpret_cast<unsigned long long*>(tally);
   a.threshold = threshold; a.nslabs = (int)slabs; a.top_k = top_k; a.batch = batch;
   hipLaunchKernelGGL(match_merge_kernel, dim3((unsigned)batch), block, 0, st, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("tf2_emb_match: launch failed: ") + hipGetErrorString(e)); return TF2_ERR_HIP; }
-  return TF2_OK;
+  return launch_result("tf2_emb_match");
 }
 
 }  // namespace tf2

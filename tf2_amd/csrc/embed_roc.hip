@@ -247,7 +247,7 @@ tf2_status check_grid(const char* who, int d, int n_thr, float step) {
 
 tf2_status emb_roc_hist(const float* rows_a, const int32_t* ids_a, int n_a, const float* rows_b, const int32_t* ids_b, int n_b, int d,
                         int n_thr, float step, int64_t* hist, void* stream) {
-  auto fail = [](const std::string& m) { set_error("tf2_emb_roc_hist: " + m); return TF2_ERR_ARG; };
+  auto fail = [](const std::string& m) { return arg_refusal("tf2_emb_roc_hist", m); };
   const tf2_status st = check_grid("tf2_emb_roc_hist", d, n_thr, step);
   if (st != TF2_OK) return st;
   if (n_a < 1) return fail("n_a must be >= 1");
@@ -267,14 +267,12 @@ tf2_status emb_roc_hist(const float* rows_a, const int32_t* ids_a, int n_a, cons
   const long long blocks = p.self ? ta * (ta + 1) / 2 : ta * tb;
   if (blocks > 0x7fffffffll) { set_error("tf2_emb_roc_hist: too many tile pairs for one grid"); return TF2_ERR_UNSUPPORTED; }
   hipLaunchKernelGGL(roc_hist_kernel, dim3((unsigned)blocks), dim3(kThreads), (size_t)2 * (n_thr + 1) * sizeof(uint32_t), (hipStream_t)stream, p);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("tf2_emb_roc_hist: launch failed: ") + hipGetErrorString(e)); return TF2_ERR_HIP; }
-  return TF2_OK;
+  return launch_result("tf2_emb_roc_hist");
 }
 
 tf2_status emb_roc_pairs(const float* rows, int n_rows, int d, const int32_t* pairs, int n_pairs, int n_folds, int n_thr, float step,
                          float* dist, int64_t* hist, int64_t* invalid, void* stream) {
-  auto fail = [](const std::string& m) { set_error("tf2_emb_roc_pairs: " + m); return TF2_ERR_ARG; };
+  auto fail = [](const std::string& m) { return arg_refusal("tf2_emb_roc_pairs", m); };
   const tf2_status st = check_grid("tf2_emb_roc_pairs", d, n_thr, step);
   if (st != TF2_OK) return st;
   if (n_rows < 1) return fail("n_rows must be >= 1");
@@ -288,9 +286,7 @@ tf2_status emb_roc_pairs(const float* rows, int n_rows, int d, const int32_t* pa
   p.invalid = reinterpret_cast<unsigned long long*>(invalid);
   p.step = step; p.n_rows = n_rows; p.d = d; p.n_pairs = n_pairs; p.n_folds = n_folds; p.n_thr = n_thr;
   hipLaunchKernelGGL(roc_pairs_kernel, dim3((unsigned)(((long long)n_pairs + kWaves - 1) / kWaves)), dim3(kThreads), 0, (hipStream_t)stream, p);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("tf2_emb_roc_pairs: launch failed: ") + hipGetErrorString(e)); return TF2_ERR_HIP; }
-  return TF2_OK;
+  return launch_result("tf2_emb_roc_pairs");
 }
 
 }  // namespace tf2

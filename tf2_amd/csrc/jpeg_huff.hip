@@ -612,7 +612,7 @@ size_t jpeg_huff_work_bytes(const tf2_jpeg_huff_desc* d, int batch, size_t max_s
 tf2_status jpeg_huff(const tf2_jpeg_huff_desc* d, const uint8_t* bytes, size_t bytes_len, const tf2_jpeg_scan* scan,
                      const tf2_jpeg_src* jpeg, int16_t* coef, size_t coef_blocks, uint8_t* work, size_t work_bytes, int batch,
                      int32_t* status, void* stream) {
-  auto refuse = [](const std::string& m) { set_error("tf2_jpeg_huff: " + m); return TF2_ERR_ARG; };
+  auto refuse = [](const std::string& m) { return arg_refusal("tf2_jpeg_huff", m); };
   if (!d) return refuse("null desc");
   if (d->size != sizeof(tf2_jpeg_huff_desc)) return refuse("desc size " + std::to_string(d->size) + ", expected sizeof(tf2_jpeg_huff_desc)");
   if (d->layout != TF2_YCC_PLANAR && d->layout != TF2_YCC_GRAY) return refuse("layout must be TF2_YCC_PLANAR or TF2_YCC_GRAY");
@@ -647,9 +647,7 @@ tf2_status jpeg_huff(const tf2_jpeg_huff_desc* d, const uint8_t* bytes, size_t b
   a.my = gray ? 1 : d->sub_y;
   a.lanes = jpeg_huff_chunk_lanes(1 << a.slog);
   hipLaunchKernelGGL(jpeg_huff_kernel, dim3((unsigned)batch), dim3(kHuffThreads), 0, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("tf2_jpeg_huff: launch failed: ") + hipGetErrorString(e)); return TF2_ERR_HIP; }
-  return TF2_OK;
+  return launch_result("tf2_jpeg_huff");
 }
 
 }  // namespace tf2

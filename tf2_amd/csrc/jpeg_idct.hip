@@ -187,7 +187,7 @@ __global__ __launch_bounds__(kJpegThreads) void jpeg_idct_kernel(JpegArgs a) {
 tf2_status jpeg_idct(const tf2_jpeg_desc* d, const int16_t* coef, size_t coef_blocks, const tf2_jpeg_src* jpeg, const uint16_t* quant,
                      uint8_t* planes, size_t planes_bytes, const tf2_ycc_src* ycc, const tf2_image_src* srcs, int batch,
                      int32_t* status, void* stream) {
-  auto refuse = [](const std::string& m) { set_error("tf2_jpeg_idct: " + m); return TF2_ERR_ARG; };
+  auto refuse = [](const std::string& m) { return arg_refusal("tf2_jpeg_idct", m); };
   if (!d) return refuse("null desc");
   if (d->size != sizeof(tf2_jpeg_desc)) return refuse("desc size " + std::to_string(d->size) + ", expected sizeof(tf2_jpeg_desc)");
   if (d->layout != TF2_YCC_PLANAR && d->layout != TF2_YCC_GRAY) return refuse("layout must be TF2_YCC_PLANAR or TF2_YCC_GRAY");
@@ -216,9 +216,7 @@ tf2_status jpeg_idct(const tf2_jpeg_desc* d, const int16_t* coef, size_t coef_bl
   const dim3 grid((unsigned)blocks), block(kJpegThreads);
   if (gray) hipLaunchKernelGGL((jpeg_idct_kernel<1>), grid, block, 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL((jpeg_idct_kernel<3>), grid, block, 0, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("tf2_jpeg_idct: launch failed: ") + hipGetErrorString(e)); return TF2_ERR_HIP; }
-  return TF2_OK;
+  return launch_result("tf2_jpeg_idct");
 }
 
 }  // namespace tf2

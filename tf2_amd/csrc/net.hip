@@ -21,6 +21,13 @@ namespace tf2 {
 static thread_local std::string g_err;
 void set_error(const std::string& s) { g_err = s; }
 const std::string& last_error() { return g_err; }
+tf2_status arg_refusal(const char* fn, const std::string& what) { set_error(std::string(fn) + ": " + what); return TF2_ERR_ARG; }
+tf2_status launch_result(const char* fn) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return TF2_OK;
+  set_error(std::string(fn) + ": launch failed: " + hipGetErrorString(e));
+  return TF2_ERR_HIP;
+}
 
 #define HIP_OK(expr)                                                                   \
   do {                                                                                 \
@@ -446,7 +453,7 @@ int Net::issue(const Launch& st, const LaunchPlan* lp, const void* images, bool 
 tf2_status Net::describe_launches(int batch, bool concurrent, std::vector<std::pair<int, LaunchRecord>>* out) {
   std::lock_guard<std::mutex> lock(run_mutex);
   if (!packed_valid) { set_error("tf2_net_describe_launches: no packed image"); return TF2_ERR_STATE; }
-  if (batch <= 0) { set_error("tf2_net_describe_launches: batch must be positive"); return TF2_ERR_ARG; }
+  if (batch <= 0) return arg_refusal("tf2_net_describe_launches", "batch must be positive");
   const WorkPlan* wp = plan(batch, false);
   // the description's plan is built beside the cache (never evicts or replaces a run plan) and dropped again
   const uint8_t* saved = packed_dev;
@@ -480,7 +487,7 @@ tf2_status Net::describe_launches(int batch, bool concurrent, std::vector<std::p
 tf2_status Net::describe_workspace(int batch, bool keep_all, std::vector<TensorPlan>* tensors, std::vector<LayerExec>* rows) {
   std::lock_guard<std::mutex> lock(run_mutex);
   if (!packed_valid) { set_error("tf2_net_describe_workspace: no packed image"); return TF2_ERR_STATE; }
-  if (batch <= 0) { set_error("tf2_net_describe_workspace: batch must be positive"); return TF2_ERR_ARG; }
+  if (batch <= 0) return arg_refusal("tf2_net_describe_workspace", "batch must be positive");
   const WorkPlan* wp = plan(batch, keep_all);
   *tensors = wp->tensors;
   *rows = wp->exec;
@@ -505,7 +512,7 @@ tf2_status Net::run(const void* images, bool images_are_q, int batch, void* ws, 
   if (!packed_valid) { set_error("tf2_net_run: no packed image (tf2_net_pack / tf2_net_packed_adopt)"); return TF2_ERR_STATE; }
   if (!packed_dev) { set_error("tf2_net_run: packed image not bound to the device (tf2_net_bind_device)"); return TF2_ERR_STATE; }
   if (q.empty()) { set_error("tf2_net_run: q table not set"); return TF2_ERR_STATE; }
-  if (batch <= 0) { set_error("tf2_net_run: batch must be positive"); return TF2_ERR_ARG; }
+  if (batch <= 0) return arg_refusal("tf2_net_run", "batch must be positive");
   // keep_all plans are a superset in size; pick whichever plan fits the caller's buffer
   const WorkPlan* wp = nullptr;
   if (outputs_kept) {
@@ -622,7 +629,7 @@ tf2_status Net::run(const void* images, bool images_are_q, int batch, void* ws, 
 // function of the batch alone, so the caller names the batch the workspace was used for.
 tf2_status Net::poll_error(int batch, void* ws, size_t ws_bytes, void* stream) {
   if (!packed_valid || !packed_dev) { set_error("tf2_net_poll_error: no packed model bound"); return TF2_ERR_STATE; }
-  if (batch <= 0 || !ws) { set_error("tf2_net_poll_error: bad argument"); return TF2_ERR_ARG; }
+  if (batch <= 0 || !ws) return arg_refusal("tf2_net_poll_error", "bad argument");
   const WorkPlan* wp = nullptr;
   auto ito = outputs_ws.find(ws);
   if (ito != outputs_ws.end() && ito->second == batch) {
@@ -669,8 +676,8 @@ void Net::drain_profile() {
 
 tf2_status Net::read_layer(int layer, int batch, const void* ws, int8_t* dst, size_t cap, void* stream) {
   // the keep_all plan of this batch (planning is deterministic: rebuilt if tf2_net_reload_options dropped it since the run)
-  if (batch <= 0) { set_error("tf2_net_read_layer: batch must be positive"); return TF2_ERR_ARG; }
-  if (layer < -1 || layer >= nd.n_layers) { set_error("tf2_net_read_layer: bad layer"); return TF2_ERR_ARG; }
+  if (batch <= 0) return arg_refusal("tf2_net_read_layer", "batch must be positive");
+  if (layer < -1 || layer >= nd.n_layers) return arg_refusal("tf2_net_read_layer", "bad layer");
   const WorkPlan* wpp;
   { std::lock_guard<std::mutex> lock(run_mutex); wpp = plan(batch, true); }        // (std::map nodes are stable: the plan outlives the lock)
   const WorkPlan& wp = *wpp;

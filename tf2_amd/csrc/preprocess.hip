@@ -14,37 +14,24 @@
 #include <string>
 #include "tf2_device.h"
 #include "tf2_net.h"
-#include "resample.h"
-#include "preprocess.h"
+#include "image_input.h"
 
 namespace tf2 {
 
 namespace {
 
-struct PreprocessArgs {
-  const uint8_t* pixels;
-  unsigned long long pixels_bytes;
-  const tf2_image_src* srcs;
-  void* out;
-  int32_t* status;
-  int OH, OW, plane, blocks_per_image;
-  int pb, ch0, ch1, ch2, round_resized;
-  float mean0, mean1, mean2, scale0, scale1, scale2, trans;
-};
-
 template <bool OUT_Q, bool VEC>
-__global__ __launch_bounds__(kPrepThreads) void preprocess_kernel(PreprocessArgs a) {
-  const int b = blockIdx.x / a.blocks_per_image;
-  const int p0 = (blockIdx.x - b * a.blocks_per_image) * kPrepBlockPix + threadIdx.x * kPrepPix;
+__global__ __launch_bounds__(kPrepThreads) void preprocess_kernel(ImageArgs a, int blocks_per_image) {
+  int b, p0;
+  bool first;
+  gather_thread(blocks_per_image, b, p0, first);
   const tf2_image_src r = a.srcs[b];
   const int st = record_status(r, a.pb, a.pixels_bytes, a.OH, a.OW);
-  if (blockIdx.x == b * a.blocks_per_image && threadIdx.x == 0) a.status[b] = st;
+  if (first) a.status[b] = st;
 
   float v[3][kPrepPix];
-  if (st != 0) {
-    for (int c = 0; c < 3; c++)
-      for (int j = 0; j < kPrepPix; j++) v[c][j] = 0.0f;
-  } else {
+  if (st != 0) zero_px(v);
+  else {
     const uint8_t* const base = a.pixels + r.offset;
     const double ry = (double)r.h / (double)r.resize_h, rx = (double)r.w / (double)r.resize_w;
     const float mean[3] = {a.mean0, a.mean1, a.mean2}, scale[3] = {a.scale0, a.scale1, a.scale2};
@@ -86,35 +73,11 @@ std::string preprocess_refusal(const Net& net, const tf2_preprocess_desc* d, int
 
 tf2_status preprocess(const Net& net, const tf2_preprocess_desc* d, const uint8_t* pixels, size_t pixels_bytes, const tf2_image_src* srcs,
                       int batch, int out_q, void* out, int32_t* status, void* stream) {
-  auto refuse = [](const std::string& m) { set_error("tf2_preprocess: " + m); return TF2_ERR_ARG; };
-  const std::string why = preprocess_refusal(net, d, batch, out_q, pixels && srcs && out && status);
-  if (!why.empty()) return refuse(why);
-
-  PreprocessArgs a{};
-  a.pixels = pixels; a.pixels_bytes = pixels_bytes; a.srcs = srcs; a.out = out; a.status = status;
-  a.OH = net.nd.image_h; a.OW = net.nd.image_w; a.plane = a.OH * a.OW;
-  a.blocks_per_image = (a.plane + kPrepBlockPix - 1) / kPrepBlockPix;
-  a.pb = d->pixel_bytes; a.ch0 = d->src_channel[0]; a.ch1 = d->src_channel[1]; a.ch2 = d->src_channel[2];
-  a.round_resized = d->round_resized;
-  a.mean0 = d->mean[0]; a.mean1 = d->mean[1]; a.mean2 = d->mean[2];
-  a.scale0 = d->scale[0]; a.scale1 = d->scale[1]; a.scale2 = d->scale[2];
-  // 2^-Q0, read now from where prep_input reads it (q[0]); the same value as its 1 / (1 << q0) | (1 << -q0) for every |q0| <= 30
-  a.trans = out_q ? std::ldexp(1.0f, -(int)net.q[0]) : 1.0f;
-  const bool vec = (a.plane % kPrepPix == 0) && ((uintptr_t)out % (out_q ? 4 : 16) == 0);   // whole aligned 4-pixel runs
-  const long long blocks = (long long)batch * a.blocks_per_image;
-  if (blocks > 0x7fffffffLL) return refuse("batch too large for one launch");
-  const dim3 grid((unsigned)blocks), block(kPrepThreads);
-  hipStream_t s = (hipStream_t)stream;
-  if (out_q) {
-    if (vec) hipLaunchKernelGGL((preprocess_kernel<true, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((preprocess_kernel<true, false>), grid, block, 0, s, a);
-  } else {
-    if (vec) hipLaunchKernelGGL((preprocess_kernel<false, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((preprocess_kernel<false, false>), grid, block, 0, s, a);
-  }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("tf2_preprocess: launch failed: ") + hipGetErrorString(e)); return TF2_ERR_HIP; }
-  return TF2_OK;
+  std::string why = preprocess_refusal(net, d, batch, out_q, pixels && srcs && out && status);
+  if (why.empty())
+    why = launch_gather(TF2_GATHER_KERNELS(preprocess_kernel), image_args(net, d, out_q, pixels, pixels_bytes, srcs, batch, out, status),
+                        out_q, batch, "batch", stream);
+  return why.empty() ? launch_result("tf2_preprocess") : arg_refusal("tf2_preprocess", why);
 }
 
 }  // namespace tf2

@@ -18,8 +18,7 @@
 #include <string>
 #include "tf2_device.h"
 #include "tf2_net.h"
-#include "resample.h"
-#include "preprocess.h"
+#include "image_input.h"
 #include "roi_crop.h"
 
 namespace tf2 {
@@ -135,41 +134,19 @@ __global__ __launch_bounds__(kSelThreads) void roi_select_kernel(RoiSelectArgs a
   if (tid == 0) a.roi_counts[b] = n;
 }
 
-struct RoiCropArgs {
-  const uint8_t* pixels;
-  unsigned long long pixels_bytes;
-  const tf2_image_src* srcs;
-  const tf2_roi* rois;
-  void* out;
-  int32_t* status;
-  int batch, OH, OW, plane, blocks_per_image;
-  int pb, ch0, ch1, ch2, round_resized;
-  float mean0, mean1, mean2, scale0, scale1, scale2, trans;
-};
-
 template <bool OUT_Q, bool VEC>
-__global__ __launch_bounds__(kPrepThreads) void roi_crop_kernel(RoiCropArgs a) {
-  const int s = blockIdx.x / a.blocks_per_image;
-  const int p0 = (blockIdx.x - s * a.blocks_per_image) * kPrepBlockPix + threadIdx.x * kPrepPix;
-  const tf2_roi R = a.rois[s];
+__global__ __launch_bounds__(kPrepThreads) void roi_crop_kernel(ImageArgs a, int blocks_per_image, const tf2_roi* rois) {
+  int s, p0;
+  bool first;
+  gather_thread(blocks_per_image, s, p0, first);
+  const tf2_roi R = rois[s];
   tf2_image_src r{};
-  int st = 0;
-  if (R.image == -1) st = TF2_ROI_EMPTY;
-  else {
-    if (R.image < 0 || R.image >= a.batch) st |= TF2_ROI_BAD_IMAGE;
-    else {
-      r = a.srcs[R.image];
-      if (src_status(r, a.pb, a.pixels_bytes) != 0) st |= TF2_ROI_BAD_SRC;
-    }
-    if (!box_ok(R.x0, R.y0, R.x1, R.y1)) st |= TF2_ROI_BAD_BOX;
-  }
-  if (blockIdx.x == s * a.blocks_per_image && threadIdx.x == 0) a.status[s] = st;
+  const int st = slot_source(a, R.image, box_ok(R.x0, R.y0, R.x1, R.y1) ? 0 : TF2_ROI_BAD_BOX, r);
+  if (first) a.status[s] = st;
 
   float v[3][kPrepPix];
-  if (st != 0) {
-    for (int c = 0; c < 3; c++)
-      for (int j = 0; j < kPrepPix; j++) v[c][j] = 0.0f;
-  } else {
+  if (st != 0) zero_px(v);
+  else {
     const uint8_t* const base = a.pixels + r.offset;
     const double sy = ((double)R.y1 - (double)R.y0) / (double)a.OH, sx = ((double)R.x1 - (double)R.x0) / (double)a.OW;
     const float mean[3] = {a.mean0, a.mean1, a.mean2}, scale[3] = {a.scale0, a.scale1, a.scale2};
@@ -195,7 +172,7 @@ __global__ __launch_bounds__(kPrepThreads) void roi_crop_kernel(RoiCropArgs a) {
 
 tf2_status roi_select(const tf2_roi_desc* d, const float* det, const int32_t* counts, const tf2_image_src* srcs, int batch, tf2_roi* rois,
                       int32_t* roi_counts, void* stream) {
-  auto refuse = [](const std::string& m) { set_error("tf2_roi_select: " + m); return TF2_ERR_ARG; };
+  auto refuse = [](const std::string& m) { return arg_refusal("tf2_roi_select", m); };
   if (!d) return refuse("null desc");
   if (d->size != sizeof(tf2_roi_desc)) return refuse("desc size " + std::to_string(d->size) + ", expected sizeof(tf2_roi_desc)");
   if (d->num_classes < 2 || d->num_classes > 256) return refuse("num_classes must be in 2..256");
@@ -223,42 +200,17 @@ tf2_status roi_select(const tf2_roi_desc* d, const float* det, const int32_t* co
   for (int k = 0; k < 8; k++) a.mask[k] = d->class_mask[k];
   a.min_score = d->min_score; a.expand_w = d->expand_w; a.expand_h = d->expand_h;
   hipLaunchKernelGGL(roi_select_kernel, dim3((unsigned)batch), dim3(kSelThreads), 0, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("tf2_roi_select: launch failed: ") + hipGetErrorString(e)); return TF2_ERR_HIP; }
-  return TF2_OK;
+  return launch_result("tf2_roi_select");
 }
 
 tf2_status roi_crop(const Net& net2, const tf2_preprocess_desc* d, const uint8_t* pixels, size_t pixels_bytes, const tf2_image_src* srcs,
                     int batch, const tf2_roi* rois, int n_slots, int out_q, void* out, int32_t* status, void* stream) {
-  auto refuse = [](const std::string& m) { set_error("tf2_roi_crop: " + m); return TF2_ERR_ARG; };
-  const std::string why = preprocess_refusal(net2, d, batch, out_q, pixels && srcs && out && status && rois);
-  if (!why.empty()) return refuse(why);
-  if (n_slots < 1) return refuse("n_slots must be >= 1");
-
-  RoiCropArgs a{};
-  a.pixels = pixels; a.pixels_bytes = pixels_bytes; a.srcs = srcs; a.rois = rois; a.out = out; a.status = status;
-  a.batch = batch; a.OH = net2.nd.image_h; a.OW = net2.nd.image_w; a.plane = a.OH * a.OW;
-  a.blocks_per_image = (a.plane + kPrepBlockPix - 1) / kPrepBlockPix;
-  a.pb = d->pixel_bytes; a.ch0 = d->src_channel[0]; a.ch1 = d->src_channel[1]; a.ch2 = d->src_channel[2];
-  a.round_resized = d->round_resized;
-  a.mean0 = d->mean[0]; a.mean1 = d->mean[1]; a.mean2 = d->mean[2];
-  a.scale0 = d->scale[0]; a.scale1 = d->scale[1]; a.scale2 = d->scale[2];
-  a.trans = out_q ? std::ldexp(1.0f, -(int)net2.q[0]) : 1.0f;          // 2^-Q0, read now, as tf2_preprocess does
-  const bool vec = (a.plane % kPrepPix == 0) && ((uintptr_t)out % (out_q ? 4 : 16) == 0);   // whole aligned 4-pixel runs
-  const long long blocks = (long long)n_slots * a.blocks_per_image;
-  if (blocks > 0x7fffffffLL) return refuse("n_slots too large for one launch");
-  const dim3 grid((unsigned)blocks), block(kPrepThreads);
-  hipStream_t s = (hipStream_t)stream;
-  if (out_q) {
-    if (vec) hipLaunchKernelGGL((roi_crop_kernel<true, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((roi_crop_kernel<true, false>), grid, block, 0, s, a);
-  } else {
-    if (vec) hipLaunchKernelGGL((roi_crop_kernel<false, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((roi_crop_kernel<false, false>), grid, block, 0, s, a);
-  }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("tf2_roi_crop: launch failed: ") + hipGetErrorString(e)); return TF2_ERR_HIP; }
-  return TF2_OK;
+  std::string why = preprocess_refusal(net2, d, batch, out_q, pixels && srcs && out && status && rois);
+  if (why.empty() && n_slots < 1) why = "n_slots must be >= 1";
+  if (why.empty())
+    why = launch_gather(TF2_GATHER_KERNELS(roi_crop_kernel), image_args(net2, d, out_q, pixels, pixels_bytes, srcs, batch, out, status),
+                        out_q, n_slots, "n_slots", stream, rois);
+  return why.empty() ? launch_result("tf2_roi_crop") : arg_refusal("tf2_roi_crop", why);
 }
 
 }  // namespace tf2

@@ -16,8 +16,7 @@
 #include <string>
 #include "tf2_device.h"
 #include "tf2_net.h"
-#include "resample.h"
-#include "preprocess.h"
+#include "image_input.h"
 #include "roi_crop.h"
 #include "roi_warp.h"
 
@@ -101,45 +100,23 @@ __global__ __launch_bounds__(kFitThreads) void roi_fit_kernel(RoiFitArgs a) {
   a.status[s] = st;
 }
 
-struct RoiWarpArgs {
-  const uint8_t* pixels;
-  unsigned long long pixels_bytes;
-  const tf2_image_src* srcs;
-  const tf2_roi_xform* xf;
-  void* out;
-  int32_t* status;
-  int batch, OW, plane, blocks_per_image;
-  int pb, ch0, ch1, ch2;
-  float mean0, mean1, mean2, scale0, scale1, scale2, trans;
-};
-
 // Pillow's BILINEAR(v, a, b, d): the difference in integers, one product and one sum in double
 __device__ __forceinline__ double lerp_u8(int p, int q, double d) { return (double)p + (double)(q - p) * d; }
 
 template <bool OUT_Q, bool VEC>
-__global__ __launch_bounds__(kPrepThreads) void roi_warp_kernel(RoiWarpArgs a) {
-  const int s = blockIdx.x / a.blocks_per_image;
-  const int p0 = (blockIdx.x - s * a.blocks_per_image) * kPrepBlockPix + threadIdx.x * kPrepPix;
-  const tf2_roi_xform T = a.xf[s];
+__global__ __launch_bounds__(kPrepThreads) void roi_warp_kernel(ImageArgs a, int blocks_per_image, const tf2_roi_xform* xf) {
+  int s, p0;
+  bool first;
+  gather_thread(blocks_per_image, s, p0, first);
+  const tf2_roi_xform T = xf[s];
   tf2_image_src r{};
-  int st = 0;
-  if (T.image == -1) st = TF2_ROI_EMPTY;
-  else {
-    if (T.image < 0 || T.image >= a.batch) st |= TF2_ROI_BAD_IMAGE;
-    else {
-      r = a.srcs[T.image];
-      if (src_status(r, a.pb, a.pixels_bytes) != 0) st |= TF2_ROI_BAD_SRC;
-    }
-    if (!(finite_d(T.m[0]) && finite_d(T.m[1]) && finite_d(T.m[2]) && finite_d(T.m[3]) && finite_d(T.m[4]) && finite_d(T.m[5])))
-      st |= TF2_ROI_BAD_MATRIX;
-  }
-  if (blockIdx.x == s * a.blocks_per_image && threadIdx.x == 0) a.status[s] = st;
+  const bool finite = finite_d(T.m[0]) && finite_d(T.m[1]) && finite_d(T.m[2]) && finite_d(T.m[3]) && finite_d(T.m[4]) && finite_d(T.m[5]);
+  const int st = slot_source(a, T.image, finite ? 0 : TF2_ROI_BAD_MATRIX, r);
+  if (first) a.status[s] = st;
 
   float v[3][kPrepPix];
-  if (st != 0) {
-    for (int c = 0; c < 3; c++)
-      for (int j = 0; j < kPrepPix; j++) v[c][j] = 0.0f;
-  } else {
+  if (st != 0) zero_px(v);
+  else {
     const uint8_t* const base = a.pixels + r.offset;
     const double w = (double)r.w, h = (double)r.h;
     const float mean[3] = {a.mean0, a.mean1, a.mean2}, scale[3] = {a.scale0, a.scale1, a.scale2};
@@ -179,7 +156,7 @@ __global__ __launch_bounds__(kPrepThreads) void roi_warp_kernel(RoiWarpArgs a) {
 
 tf2_status roi_fit(const tf2_roi_fit_desc* d, const tf2_roi* rois, const float* lmk, int n_slots, tf2_roi_xform* xf, int32_t* status,
                    void* stream) {
-  auto refuse = [](const std::string& m) { set_error("tf2_roi_fit: " + m); return TF2_ERR_ARG; };
+  auto refuse = [](const std::string& m) { return arg_refusal("tf2_roi_fit", m); };
   if (!d) return refuse("null desc");
   if (d->size != sizeof(tf2_roi_fit_desc)) return refuse("desc size " + std::to_string(d->size) + ", expected sizeof(tf2_roi_fit_desc)");
   if (d->n_points < 2 || d->n_points > kFitMaxPoints) return refuse("n_points must be in 2..16");
@@ -206,42 +183,18 @@ tf2_status roi_fit(const tf2_roi_fit_desc* d, const tf2_roi* rois, const float* 
   for (int i = 0; i < K; i++) { a.tpl[i][0] = d->tpl[i][0]; a.tpl[i][1] = d->tpl[i][1]; }
   const unsigned blocks = (unsigned)(((long long)n_slots + kFitThreads - 1) / kFitThreads);
   hipLaunchKernelGGL(roi_fit_kernel, dim3(blocks), dim3(kFitThreads), 0, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("tf2_roi_fit: launch failed: ") + hipGetErrorString(e)); return TF2_ERR_HIP; }
-  return TF2_OK;
+  return launch_result("tf2_roi_fit");
 }
 
 tf2_status roi_warp(const Net& net2, const tf2_preprocess_desc* d, const uint8_t* pixels, size_t pixels_bytes, const tf2_image_src* srcs,
                     int batch, const tf2_roi_xform* xf, int n_slots, int out_q, void* out, int32_t* status, void* stream) {
-  auto refuse = [](const std::string& m) { set_error("tf2_roi_warp: " + m); return TF2_ERR_ARG; };
-  const std::string why = preprocess_refusal(net2, d, batch, out_q, pixels && srcs && out && status && xf);
-  if (!why.empty()) return refuse(why);
-  if (n_slots < 1) return refuse("n_slots must be >= 1");
-  if ((uintptr_t)xf % alignof(tf2_roi_xform) != 0) return refuse("xf_dev must be 8-byte aligned");
-
-  RoiWarpArgs a{};
-  a.pixels = pixels; a.pixels_bytes = pixels_bytes; a.srcs = srcs; a.xf = xf; a.out = out; a.status = status;
-  a.batch = batch; a.OW = net2.nd.image_w; a.plane = net2.nd.image_h * net2.nd.image_w;
-  a.blocks_per_image = (a.plane + kPrepBlockPix - 1) / kPrepBlockPix;
-  a.pb = d->pixel_bytes; a.ch0 = d->src_channel[0]; a.ch1 = d->src_channel[1]; a.ch2 = d->src_channel[2];
-  a.mean0 = d->mean[0]; a.mean1 = d->mean[1]; a.mean2 = d->mean[2];
-  a.scale0 = d->scale[0]; a.scale1 = d->scale[1]; a.scale2 = d->scale[2];
-  a.trans = out_q ? std::ldexp(1.0f, -(int)net2.q[0]) : 1.0f;          // 2^-Q0, read now, as tf2_roi_crop does
-  const bool vec = (a.plane % kPrepPix == 0) && ((uintptr_t)out % (out_q ? 4 : 16) == 0);   // whole aligned 4-pixel runs
-  const long long blocks = (long long)n_slots * a.blocks_per_image;
-  if (blocks > 0x7fffffffLL) return refuse("n_slots too large for one launch");
-  const dim3 grid((unsigned)blocks), block(kPrepThreads);
-  hipStream_t s = (hipStream_t)stream;
-  if (out_q) {
-    if (vec) hipLaunchKernelGGL((roi_warp_kernel<true, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((roi_warp_kernel<true, false>), grid, block, 0, s, a);
-  } else {
-    if (vec) hipLaunchKernelGGL((roi_warp_kernel<false, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((roi_warp_kernel<false, false>), grid, block, 0, s, a);
-  }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("tf2_roi_warp: launch failed: ") + hipGetErrorString(e)); return TF2_ERR_HIP; }
-  return TF2_OK;
+  std::string why = preprocess_refusal(net2, d, batch, out_q, pixels && srcs && out && status && xf);
+  if (why.empty() && n_slots < 1) why = "n_slots must be >= 1";
+  if (why.empty() && (uintptr_t)xf % alignof(tf2_roi_xform) != 0) why = "xf_dev must be 8-byte aligned";
+  if (why.empty())
+    why = launch_gather(TF2_GATHER_KERNELS(roi_warp_kernel), image_args(net2, d, out_q, pixels, pixels_bytes, srcs, batch, out, status),
+                        out_q, n_slots, "n_slots", stream, xf);
+  return why.empty() ? launch_result("tf2_roi_warp") : arg_refusal("tf2_roi_warp", why);
 }
 
 }  // namespace tf2

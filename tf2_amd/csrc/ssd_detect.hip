@@ -338,7 +338,7 @@ SsdDetector::~SsdDetector() {
 }
 
 tf2_status SsdDetector::create(Net* n, const tf2_ssd_desc* d) {
-  auto fail = [](const std::string& m) { set_error("tf2_ssd_create: " + m); return TF2_ERR_ARG; };
+  auto fail = [](const std::string& m) { return arg_refusal("tf2_ssd_create", m); };
   if (!d || d->size < sizeof(tf2_ssd_desc)) return fail("desc missing or older than this library's tf2_ssd_desc");
   if (!n->packed_valid) { set_error("tf2_ssd_create: no packed image (tf2_net_pack / tf2_net_packed_adopt first)"); return TF2_ERR_STATE; }
   if (n->q.empty()) { set_error("tf2_ssd_create: q table not set"); return TF2_ERR_STATE; }
@@ -420,8 +420,8 @@ size_t SsdDetector::detect_scratch_size(int batch) const { return batch <= 0 ? 0
 
 tf2_status SsdDetector::run(const void* images, bool images_are_q, int batch, void* ws, size_t ws_bytes, float* det, int32_t* counts,
                             float* boxes_out, float* scores_out, int8_t* logits, void* mark_event, void* stream) {
-  if (batch <= 0) { set_error("tf2_ssd_run: batch must be positive"); return TF2_ERR_ARG; }
-  if (!images || !ws || !det || !counts) { set_error("tf2_ssd_run: null device pointer"); return TF2_ERR_ARG; }
+  if (batch <= 0) return arg_refusal("tf2_ssd_run", "batch must be positive");
+  if (!images || !ws || !det || !counts) return arg_refusal("tf2_ssd_run", "null device pointer");
   const size_t need = workspace_size(batch);
   if (ws_bytes < need) { set_error("tf2_ssd_run: workspace too small (tf2_ssd_workspace_size: " + std::to_string(need) + ")"); return TF2_ERR_SIZE; }
   if (tf2_status st = net->run(images, images_are_q, batch, ws, ws_bytes, logits, stream, -1, nullptr, -1, true)) return st;
@@ -453,8 +453,8 @@ tf2_status SsdDetector::run(const void* images, bool images_are_q, int batch, vo
 
 tf2_status SsdDetector::detect(const float* boxes, const float* scores, int batch, void* scratch, size_t scratch_bytes, float* det,
                                int32_t* counts, void* stream) {
-  if (batch <= 0) { set_error("tf2_ssd_detect: batch must be positive"); return TF2_ERR_ARG; }
-  if (!boxes || !scores || !scratch || !det || !counts) { set_error("tf2_ssd_detect: null device pointer"); return TF2_ERR_ARG; }
+  if (batch <= 0) return arg_refusal("tf2_ssd_detect", "batch must be positive");
+  if (!boxes || !scores || !scratch || !det || !counts) return arg_refusal("tf2_ssd_detect", "null device pointer");
   if (scratch_bytes < detect_scratch_size(batch)) { set_error("tf2_ssd_detect: scratch too small (tf2_ssd_detect_scratch_size)"); return TF2_ERR_SIZE; }
   float* probs = (float*)scratch;
   if (launch_ssd_transpose(scores, probs, batch, P, C, stream)) { set_error("tf2_ssd_detect: transpose launch failed"); return TF2_ERR_HIP; }

@@ -181,7 +181,7 @@ __global__ __launch_bounds__(kEvalThreads) void det_eval_kernel(DetEvalArgs a) {
 }  // namespace
 
 tf2_status DetEvaluator::create(const tf2_det_eval_desc* d) {
-  auto fail = [](const std::string& m) { set_error("tf2_det_eval_create: " + m); return TF2_ERR_ARG; };
+  auto fail = [](const std::string& m) { return arg_refusal("tf2_det_eval_create", m); };
   if (!d || d->size != sizeof(tf2_det_eval_desc)) return fail("desc size: missing, or not sizeof(tf2_det_eval_desc)");
   if (d->num_classes < 2 || d->num_classes > kEvalMaxClasses) return fail("num_classes must be in 2.." + std::to_string(kEvalMaxClasses));
   if (d->top_k < 1 || d->top_k > kEvalMaxTopK) return fail("top_k must be in 1.." + std::to_string(kEvalMaxTopK));
@@ -193,7 +193,7 @@ tf2_status DetEvaluator::create(const tf2_det_eval_desc* d) {
 }
 
 tf2_status DetEvaluator::store_init(void* store, size_t store_bytes, void* stream) const {
-  if (!store) { set_error("tf2_det_eval_store_init: null store_dev"); return TF2_ERR_ARG; }
+  if (!store) return arg_refusal("tf2_det_eval_store_init", "null store_dev");
   if (store_bytes < store_size()) {
     set_error("tf2_det_eval_store_init: store of " + std::to_string(store_bytes) + " bytes, tf2_det_eval_store_size is " + std::to_string(store_size()));
     return TF2_ERR_ARG;
@@ -221,17 +221,15 @@ tf2_status DetEvaluator::run(const float* det, const int32_t* counts, const tf2_
   a.C = C; a.K = K; a.max_gt = max_gt; a.capacity = capacity; a.groups = (C + kEvalWaves - 1) / kEvalWaves;
   a.iou_thresh = iou_thresh;
   const long long blocks = (long long)batch * a.groups;
-  if (blocks > 0x7fffffffLL) { set_error("tf2_det_eval_run: batch too large for one launch"); return TF2_ERR_ARG; }
+  if (blocks > 0x7fffffffLL) return arg_refusal("tf2_det_eval_run", "batch too large for one launch");
   hipLaunchKernelGGL(det_eval_kernel, dim3((unsigned)blocks), dim3(kEvalThreads), 0, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("tf2_det_eval_run: launch failed: ") + hipGetErrorString(e)); return TF2_ERR_HIP; }
-  return TF2_OK;
+  return launch_result("tf2_det_eval_run");
 }
 
 // Host CPU, once per dataset.
 tf2_status DetEvaluator::summarise(const void* store_host, size_t store_bytes, int use_07_metric, tf2_det_eval_class* per_class,
                                    int64_t* images, double* map) const {
-  auto fail = [](const std::string& m) { set_error("tf2_det_eval_summarise: " + m); return TF2_ERR_ARG; };
+  auto fail = [](const std::string& m) { return arg_refusal("tf2_det_eval_summarise", m); };
   if (!store_host || !per_class) return fail("null store_host / per_class");
   if (store_bytes < store_size()) return fail("store of " + std::to_string(store_bytes) + " bytes, tf2_det_eval_store_size is " + std::to_string(store_size()));
   const uint8_t* const base = reinterpret_cast<const uint8_t*>(store_host);

@@ -351,9 +351,9 @@ bool launched(const char* what) {
 
 tf2_status inq_step(float* w, uint8_t* mask, long long n_total, const tf2_inq_seg* segs, int n_segs, double prev, double cur, int n_values,
                     int exp_floor, uint8_t* codes, void* state, void* scratch, size_t scratch_bytes, void* stream) {
-  if (!w || !mask || !segs || !state || !scratch) { set_error("tf2_inq_step: null pointer"); return TF2_ERR_ARG; }
-  if (n_segs < 1) { set_error("tf2_inq_step: n_segs must be >= 1"); return TF2_ERR_ARG; }
-  if (n_total < 1 || n_total > (1ll << 42)) { set_error("tf2_inq_step: n_total outside 1 .. 2^42"); return TF2_ERR_ARG; }
+  if (!w || !mask || !segs || !state || !scratch) return arg_refusal("tf2_inq_step", "null pointer");
+  if (n_segs < 1) return arg_refusal("tf2_inq_step", "n_segs must be >= 1");
+  if (n_total < 1 || n_total > (1ll << 42)) return arg_refusal("tf2_inq_step", "n_total outside 1 .. 2^42");
   long long at = 0;
   for (int i = 0; i < n_segs; i++) {
     const long long o = segs[i].offset, c = segs[i].count;
@@ -364,11 +364,11 @@ tf2_status inq_step(float* w, uint8_t* mask, long long n_total, const tf2_inq_se
     }
     at = o + c;
   }
-  if (!(prev >= 0.0 && prev < 1.0)) { set_error("tf2_inq_step: prev must be in [0, 1)"); return TF2_ERR_ARG; }
-  if (!(cur >= prev && cur <= 1.0)) { set_error("tf2_inq_step: cur must be in [prev, 1]"); return TF2_ERR_ARG; }
-  if (n_values < 1 || n_values > 15) { set_error("tf2_inq_step: n_values must be in 1 .. 15"); return TF2_ERR_ARG; }
-  if (exp_floor < -150 || exp_floor > 127) { set_error("tf2_inq_step: exp_floor must be in -150 .. 127"); return TF2_ERR_ARG; }
-  if (((uintptr_t)state & 7) || ((uintptr_t)scratch & 7)) { set_error("tf2_inq_step: state and scratch must be 8-byte aligned"); return TF2_ERR_ARG; }
+  if (!(prev >= 0.0 && prev < 1.0)) return arg_refusal("tf2_inq_step", "prev must be in [0, 1)");
+  if (!(cur >= prev && cur <= 1.0)) return arg_refusal("tf2_inq_step", "cur must be in [prev, 1]");
+  if (n_values < 1 || n_values > 15) return arg_refusal("tf2_inq_step", "n_values must be in 1 .. 15");
+  if (exp_floor < -150 || exp_floor > 127) return arg_refusal("tf2_inq_step", "exp_floor must be in -150 .. 127");
+  if (((uintptr_t)state & 7) || ((uintptr_t)scratch & 7)) return arg_refusal("tf2_inq_step", "state and scratch must be 8-byte aligned");
   if (scratch_bytes < inq_scratch_size(n_segs)) {
     set_error("tf2_inq_step: scratch too small (tf2_inq_scratch_size: " + std::to_string(inq_scratch_size(n_segs)) + ")");
     return TF2_ERR_SIZE;

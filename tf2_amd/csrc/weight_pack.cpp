@@ -78,7 +78,7 @@ const PackLayer* Net::pack_layer_alt(int l) const {
 
 tf2_status Net::pack(int mode) {
   if (!model_loaded) { set_error("tf2_net_pack: load a model first"); return TF2_ERR_STATE; }
-  if (mode < 0 || mode > 2) { set_error("tf2_net_pack: mode must be 0, 1 or 2"); return TF2_ERR_ARG; }
+  if (mode < 0 || mode > 2) return arg_refusal("tf2_net_pack", "mode must be 0, 1 or 2");
   const int nl = nd.n_layers;
   packed.clear();
   Blob blob(packed);

@@ -253,7 +253,7 @@ void launch(int mode, dim3 grid, hipStream_t s, const YccArgs& a) {
 
 tf2_status ycc_to_rgb(const tf2_ycc_desc* d, const uint8_t* src, size_t src_bytes, const tf2_ycc_src* ycc, uint8_t* pixels,
                       size_t pixels_bytes, const tf2_image_src* srcs, int batch, int32_t* status, void* stream) {
-  auto refuse = [](const std::string& m) { set_error("tf2_ycc_to_rgb: " + m); return TF2_ERR_ARG; };
+  auto refuse = [](const std::string& m) { return arg_refusal("tf2_ycc_to_rgb", m); };
   if (!d) return refuse("null desc");
   if (d->size != sizeof(tf2_ycc_desc)) return refuse("desc size " + std::to_string(d->size) + ", expected sizeof(tf2_ycc_desc)");
   if (d->layout < TF2_YCC_PLANAR || d->layout > TF2_YCC_GRAY) return refuse("layout must be TF2_YCC_PLANAR, _SEMI_CBCR, _SEMI_CRCB or _GRAY");
@@ -306,9 +306,7 @@ tf2_status ycc_to_rgb(const tf2_ycc_desc* d, const uint8_t* src, size_t src_byte
   const dim3 grid((unsigned)blocks);
   if (d->pixel_bytes == 4) launch<4>(mode, grid, (hipStream_t)stream, a);
   else launch<3>(mode, grid, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("tf2_ycc_to_rgb: launch failed: ") + hipGetErrorString(e)); return TF2_ERR_HIP; }
-  return TF2_OK;
+  return launch_result("tf2_ycc_to_rgb");
 }
 
 }  // namespace tf2

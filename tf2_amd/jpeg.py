@@ -523,19 +523,18 @@ class DeviceDecoder:
     def run(self, coef, jpeg, quant, planes, ycc, srcs, stream=None, status=None):
         import torch
         from . import _lib
-        dev = coef.device
-        assert coef.dtype == torch.int16 and coef.is_contiguous() and dev.type == "cuda" and coef.dim() == 2 and coef.shape[1] == 64
-        assert planes.dtype == torch.uint8 and planes.is_contiguous() and planes.device == dev
-        assert srcs.dtype == torch.int32 and srcs.is_contiguous() and srcs.device == dev and srcs.dim() == 2 and srcs.shape[1] == P.SRC_WORDS
+        dev = _lib.expect(coef, torch.int16, cols=64)
+        _lib.expect(planes, torch.uint8, device=dev)
+        _lib.expect(srcs, torch.int32, device=dev, cols=P.SRC_WORDS)
         B = srcs.shape[0]
-        assert ycc.dtype == torch.int32 and ycc.is_contiguous() and ycc.device == dev and tuple(ycc.shape) == (B, Y.YCC_WORDS)
-        assert jpeg.dtype == torch.int32 and jpeg.is_contiguous() and jpeg.device == dev and tuple(jpeg.shape) == (B, JPEG_WORDS)
-        assert quant.dtype == torch.int16 and quant.is_contiguous() and quant.device == dev and tuple(quant.shape) == (B, 3, 64)
+        _lib.expect(ycc, torch.int32, (B, Y.YCC_WORDS), dev)
+        _lib.expect(jpeg, torch.int32, (B, JPEG_WORDS), dev)
+        _lib.expect(quant, torch.int16, (B, 3, 64), dev)
         stream = stream or torch.cuda.current_stream(dev)
         with torch.cuda.stream(stream):
             if status is None:
                 status = torch.empty(B, dtype=torch.int32, device=dev)
-            assert status.dtype == torch.int32 and status.is_contiguous() and status.device == dev and tuple(status.shape) == (B,)
+            _lib.expect(status, torch.int32, (B,), dev)
             _lib.check(_lib.lib().tf2_jpeg_idct(C.byref(self._c), coef.data_ptr(), coef.shape[0], jpeg.data_ptr(), quant.data_ptr(),
                                                 planes.data_ptr(), planes.numel(), ycc.data_ptr(), srcs.data_ptr(), B,
                                                 status.data_ptr(), stream.cuda_stream))
@@ -1068,18 +1067,17 @@ class DeviceEntropy:
     def run(self, data, scan, jpeg, coef, work, stream=None, status=None):
         import torch
         from . import _lib
-        dev = coef.device
-        assert coef.dtype == torch.int16 and coef.is_contiguous() and dev.type == "cuda" and coef.dim() == 2 and coef.shape[1] == 64
-        assert data.dtype == torch.uint8 and data.is_contiguous() and data.device == dev and data.dim() == 1
-        assert work.dtype == torch.uint8 and work.is_contiguous() and work.device == dev
-        assert scan.dtype == torch.int32 and scan.is_contiguous() and scan.device == dev and scan.dim() == 2 and scan.shape[1] == SCAN_WORDS
+        dev = _lib.expect(coef, torch.int16, cols=64)
+        _lib.expect(data, torch.uint8, device=dev, ndim=1)
+        _lib.expect(work, torch.uint8, device=dev)
+        _lib.expect(scan, torch.int32, device=dev, cols=SCAN_WORDS)
         B = scan.shape[0]
-        assert jpeg.dtype == torch.int32 and jpeg.is_contiguous() and jpeg.device == dev and tuple(jpeg.shape) == (B, JPEG_WORDS)
+        _lib.expect(jpeg, torch.int32, (B, JPEG_WORDS), dev)
         stream = stream or torch.cuda.current_stream(dev)
         with torch.cuda.stream(stream):
             if status is None:
                 status = torch.empty(B, dtype=torch.int32, device=dev)
-            assert status.dtype == torch.int32 and status.is_contiguous() and status.device == dev and tuple(status.shape) == (B,)
+            _lib.expect(status, torch.int32, (B,), dev)
             _lib.check(_lib.lib().tf2_jpeg_huff(C.byref(self._c), data.data_ptr(), data.numel(), scan.data_ptr(), jpeg.data_ptr(),
                                                 coef.data_ptr(), coef.shape[0], work.data_ptr(), work.numel(), B, status.data_ptr(),
                                                 stream.cuda_stream))

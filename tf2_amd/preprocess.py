@@ -36,6 +36,7 @@ Pillow's own bytes) and the device is bit-identical to it.  For one axis with n_
 
 `Preprocessor(net, preset)` runs the device path; `pack(images, preset, device)` builds the pixel buffer and the per-image
 records (tf2_image_src) from a list of HWC arrays, or refills buffers a captured graph reads."""
+import contextlib
 import ctypes as C
 from dataclasses import dataclass, replace
 from typing import Optional, Tuple
@@ -409,6 +410,25 @@ def reference_images(images, preset: Preset, src_order: str = "RGB", q0: Optiona
                      np.float32(preset.mean), np.float32(preset.scale), preset.round_resized, q0)[0]
 
 
+@contextlib.contextmanager
+def image_outputs(out: str, n: int, out_hw, dev, stream=None, images=None, status=None):
+    """The outputs of an image entry point (tf2_preprocess*, tf2_roi_crop*, tf2_roi_warp), as a context that makes `stream` (default:
+    the current one of `dev`) current: images int8 (out="q") or float32 [n, 3, h, w] and status int32 [n], allocated on the stream or
+    -- passed in -- checked and left alone.  Yields (images, status, stream)."""
+    import torch
+    from . import _lib
+    dtype = torch.int8 if out == "q" else torch.float32
+    stream = stream or torch.cuda.current_stream(dev)
+    with torch.cuda.stream(stream):
+        if images is None:
+            images = torch.empty(n, 3, *out_hw, dtype=dtype, device=dev)
+        if status is None:
+            status = torch.empty(n, dtype=torch.int32, device=dev)
+        _lib.expect(images, dtype, (n, 3) + tuple(out_hw), dev)
+        _lib.expect(status, torch.int32, (n,), dev)
+        yield images, status, stream
+
+
 class Preprocessor:
     """tf2_preprocess -- tf2_preprocess_aa when preset.antialias -- for `net` (a tf2_amd.network.NetWork) with `preset`, on
     sources whose pixel bytes are the letters of src_order ("RGB", "BGR", "RGBA", "BGRA"...).
@@ -426,14 +446,10 @@ class Preprocessor:
         import torch
         from . import _lib
         assert out in ("q", "f32"), out
-        dev = pixels.device
-        assert pixels.dtype == torch.uint8 and pixels.is_contiguous() and dev.type == "cuda"
-        assert srcs.dtype == torch.int32 and srcs.is_contiguous() and srcs.device == dev and srcs.dim() == 2 and srcs.shape[1] == SRC_WORDS
+        dev = _lib.expect(pixels, torch.uint8)
+        _lib.expect(srcs, torch.int32, device=dev, cols=SRC_WORDS)
         B = srcs.shape[0]
-        stream = stream or torch.cuda.current_stream(dev)
-        with torch.cuda.stream(stream):
-            res = torch.empty(B, 3, *self.out_hw, dtype=torch.int8 if out == "q" else torch.float32, device=dev)
-            status = torch.empty(B, dtype=torch.int32, device=dev)
+        with image_outputs(out, B, self.out_hw, dev, stream) as (res, status, stream):
             fn = _lib.lib().tf2_preprocess_aa if self.preset.antialias else _lib.lib().tf2_preprocess
             _lib.check(fn(self.net._h, C.byref(self.desc), pixels.data_ptr(), pixels.numel(), srcs.data_ptr(), B, int(out == "q"), res.data_ptr(),
                           status.data_ptr(), stream.cuda_stream))

@@ -317,20 +317,18 @@ class DeviceCropper:
     def select(self, det, counts, srcs, stream=None, rois=None, roi_counts=None):
         import torch
         from . import _lib
-        dev = det.device
         B = srcs.shape[0]
-        assert det.dtype == torch.float32 and det.is_contiguous() and dev.type == "cuda"
-        assert tuple(det.shape) == (B, self.num_classes, self.top_k, 5), tuple(det.shape)
-        assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.device == dev and tuple(counts.shape) == (B, self.num_classes)
-        assert srcs.dtype == torch.int32 and srcs.is_contiguous() and srcs.device == dev and srcs.dim() == 2 and srcs.shape[1] == P.SRC_WORDS
+        dev = _lib.expect(det, torch.float32, (B, self.num_classes, self.top_k, 5))
+        _lib.expect(counts, torch.int32, (B, self.num_classes), dev)
+        _lib.expect(srcs, torch.int32, device=dev, cols=P.SRC_WORDS)
         stream = stream or torch.cuda.current_stream(dev)
         with torch.cuda.stream(stream):
             if rois is None:
                 rois = torch.empty(B * self.max_rois, ROI_WORDS, dtype=torch.int32, device=dev)
             if roi_counts is None:
                 roi_counts = torch.empty(B, dtype=torch.int32, device=dev)
-            assert rois.dtype == torch.int32 and rois.is_contiguous() and rois.device == dev and tuple(rois.shape) == (B * self.max_rois, ROI_WORDS)
-            assert roi_counts.dtype == torch.int32 and roi_counts.is_contiguous() and roi_counts.device == dev and tuple(roi_counts.shape) == (B,)
+            _lib.expect(rois, torch.int32, (B * self.max_rois, ROI_WORDS), dev)
+            _lib.expect(roi_counts, torch.int32, (B,), dev)
             _lib.check(_lib.lib().tf2_roi_select(C.byref(self.roi_desc), det.data_ptr(), counts.data_ptr(), srcs.data_ptr(), B,
                                                  rois.data_ptr(), roi_counts.data_ptr(), stream.cuda_stream))
         return rois, roi_counts
@@ -339,20 +337,11 @@ class DeviceCropper:
         import torch
         from . import _lib
         assert out in ("q", "f32"), out
-        dev = pixels.device
-        assert pixels.dtype == torch.uint8 and pixels.is_contiguous() and dev.type == "cuda"
-        assert srcs.dtype == torch.int32 and srcs.is_contiguous() and srcs.device == dev and srcs.dim() == 2 and srcs.shape[1] == P.SRC_WORDS
-        assert rois.dtype == torch.int32 and rois.is_contiguous() and rois.device == dev and rois.dim() == 2 and rois.shape[1] == ROI_WORDS
+        dev = _lib.expect(pixels, torch.uint8)
+        _lib.expect(srcs, torch.int32, device=dev, cols=P.SRC_WORDS)
+        _lib.expect(rois, torch.int32, device=dev, cols=ROI_WORDS)
         B, S = srcs.shape[0], rois.shape[0]
-        dtype = torch.int8 if out == "q" else torch.float32
-        stream = stream or torch.cuda.current_stream(dev)
-        with torch.cuda.stream(stream):
-            if images is None:
-                images = torch.empty(S, 3, *self.out_hw, dtype=dtype, device=dev)
-            if status is None:
-                status = torch.empty(S, dtype=torch.int32, device=dev)
-            assert images.dtype == dtype and images.is_contiguous() and images.device == dev and tuple(images.shape) == (S, 3) + self.out_hw
-            assert status.dtype == torch.int32 and status.is_contiguous() and status.device == dev and tuple(status.shape) == (S,)
+        with P.image_outputs(out, S, self.out_hw, dev, stream, images, status) as (images, status, stream):
             fn = _lib.lib().tf2_roi_crop_aa if self.antialias else _lib.lib().tf2_roi_crop
             _lib.check(fn(self.net._h, C.byref(self.desc), pixels.data_ptr(), pixels.numel(), srcs.data_ptr(), B, rois.data_ptr(), S,
                           int(out == "q"), images.data_ptr(), status.data_ptr(), stream.cuda_stream))

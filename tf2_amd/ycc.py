@@ -341,17 +341,16 @@ class DeviceConverter:
     def run(self, src, ycc, pixels, srcs, stream=None, status=None):
         import torch
         from . import _lib
-        dev = src.device
-        assert src.dtype == torch.uint8 and src.is_contiguous() and dev.type == "cuda"
-        assert pixels.dtype == torch.uint8 and pixels.is_contiguous() and pixels.device == dev
-        assert srcs.dtype == torch.int32 and srcs.is_contiguous() and srcs.device == dev and srcs.dim() == 2 and srcs.shape[1] == P.SRC_WORDS
+        dev = _lib.expect(src, torch.uint8)
+        _lib.expect(pixels, torch.uint8, device=dev)
+        _lib.expect(srcs, torch.int32, device=dev, cols=P.SRC_WORDS)
         B = srcs.shape[0]
-        assert ycc.dtype == torch.int32 and ycc.is_contiguous() and ycc.device == dev and tuple(ycc.shape) == (B, YCC_WORDS)
+        _lib.expect(ycc, torch.int32, (B, YCC_WORDS), dev)
         stream = stream or torch.cuda.current_stream(dev)
         with torch.cuda.stream(stream):
             if status is None:
                 status = torch.empty(B, dtype=torch.int32, device=dev)
-            assert status.dtype == torch.int32 and status.is_contiguous() and status.device == dev and tuple(status.shape) == (B,)
+            _lib.expect(status, torch.int32, (B,), dev)
             _lib.check(_lib.lib().tf2_ycc_to_rgb(C.byref(self._c), src.data_ptr(), src.numel(), ycc.data_ptr(), pixels.data_ptr(),
                                                  pixels.numel(), srcs.data_ptr(), B, status.data_ptr(), stream.cuda_stream))
         return status

@@ -41,6 +41,15 @@ def build_isa(force=False):
     return [os.path.join(ISA_DIR, s + ".s") for s in SOURCES]
 
 
+def kernel_segments(name):
+    """Builds the listings and reads csrc/<name>.hip's: ({kernel symbol: private_segment_fixed_size}, the group_segment_fixed_size of
+    every kernel, the listing's text)"""
+    build_isa()
+    txt = open(os.path.join(ISA_DIR, name + ".s")).read()
+    seg = {m.group(1): int(m.group(2)) for m in re.finditer(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)", txt)}
+    return seg, [int(v) for v in re.findall(r"\.group_segment_fixed_size:\s+(\d+)", txt)], txt
+
+
 def parse_kernels(path):
     """{kernel symbol: [(text, in_asm)]} -- instructions and labels of every kernel function, in layout order"""
     kernels, cur, in_asm = {}, None, False
