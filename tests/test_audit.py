@@ -20,6 +20,13 @@ def fire_tables():
     return cfg.fire_net_tables(FIRE["image_hw"], FIRE["conv1"], FIRE["fires"], FIRE["classes"], FIRE["fc_out"], FIRE["name"])
 
 
+def long_tables(expand=8):
+    """69 table rows (70 store rows; 461 records with expand 8): more than ROWS_PER_LAUNCH, so an observer's second launch really
+    happens.  expand=16 (813 records) is the form the engine runs: tf2_net_create refuses a concat slice that does not start at a
+    multiple of 16 channels, which the second expand of a fire module with expand 8 does; the oracle and the row walk take both."""
+    return cfg.fire_net_tables(15, (8, 3, 1, 0, False), ((4, expand, False),) * 22, 6, 4, "long")
+
+
 def case_inputs(name: str, batch: int):
     """(tables, q values, model stream, images) of a named regime: what the GPU tests run and the oracle statement below audits"""
     if name == "tiny_benign":
@@ -34,6 +41,10 @@ def case_inputs(name: str, batch: int):
         t = fire_tables()
         q = synth.synth_q_values(t, 1)
         return t, q, synth.synth_model(t, q, 1), synth.synth_images(t, batch, 1, kind="float" if name == "fire_float" else "int8")
+    if name == "long":
+        t = long_tables(expand=16)
+        q = synth.synth_q_values(t, 1)
+        return t, q, synth.synth_model(t, q, 1), synth.synth_images(t, batch, 1)
     raise KeyError(name)
 
 
@@ -217,6 +228,44 @@ def test_audit_abi_refusals_and_sizes_without_a_device():
     assert run() == -2 and "not bound" in L.tf2_last_error().decode()
     assert L.tf2_audit_store_init(a._h, None, a.store_size, None) == -1
     assert L.tf2_audit_store_init(a._h, one, a.store_size - 1, None) == -3
+
+
+# ---- 6. the rows of a store: one walk (_observe.store_rows) behind the three modules' rows_of ------------------------------------------------
+@pytest.mark.parametrize("tables", [cfg.tiny_tables, fire_tables, lambda: cfg.ssd300_tables(width_div=4), long_tables],
+                         ids=["tiny", "fire", "ssd300_div4", "long"])
+def test_the_three_modules_lay_out_the_same_rows(tables):
+    from tf2_amd import caq as Q, fidelity as F
+    plan = cfg.build_plan(tables())
+    chw = (plan[0].C, plan[0].H, plan[0].W)
+    a, f, c = A.rows_of(plan, chw), F.rows_of(plan, chw), Q.rows_of(plan, chw)
+    assert len(a) == len(f) == len(c) == len(plan) + 1
+    assert [r["layer"] for r in c] == [-1] + [L.index for L in plan] and (c[0]["C"], c[0]["HW"], c[0]["first"]) == (chw[0], chw[1] * chw[2], 0)
+    for ra, rf, rc in zip(a, f, c):
+        assert ra["layer"] == rf["layer"] == rc["layer"] and ra["C"] == rf["C"] == rc["C"] > 0, (ra, rf, rc)
+        assert ra["H"] * ra["W"] == rf["H"] * rf["W"] == rc["HW"] > 0, (ra, rf, rc)
+        assert ra["offset"] == rc["first"] * A.SLOTS * 8 and rf["offset"] == rc["first"] * F.SLOTS * 8, (ra, rf, rc)
+    for prev, cur in zip(c, c[1:]):
+        assert cur["first"] == prev["first"] + prev["C"]                     # a row's channels are contiguous, the rows in order
+    records = chw[0] + sum(L.N for L in plan)
+    assert c[-1]["first"] + c[-1]["C"] == records                            # the last row ends at the store size
+    assert a[-1]["offset"] + a[-1]["C"] * A.SLOTS * 8 == records * A.SLOTS * 8 and f[-1]["offset"] + f[-1]["C"] * F.SLOTS * 8 == records * F.SLOTS * 8
+    assert _lib.lib().tf2_caq_range_store_size(records) == records * Q.RANGE_SLOTS * 8
+    assert _lib.lib().tf2_caq_error_store_size(records) == records * Q.ERROR_SLOTS * 8
+    if tables is long_tables:
+        assert len(c) == 70 > max(A.ROWS_PER_LAUNCH, F.ROWS_PER_LAUNCH, Q.ROWS_PER_LAUNCH) and records == 461
+
+
+def test_the_engine_takes_the_long_program_of_the_gpu_tests():
+    """case_inputs("long") on a handle without a device: 70 rows as rows_of lays them out, more than one launch takes"""
+    from tf2_amd import fidelity as F
+    t, q, model, _ = case_inputs("long", 2)
+    net = network.NetWork(t)
+    net.Quantization(synth.q_text(q)); net.LoadModel(model); net.Pack(0)
+    plan = cfg.build_plan(t)
+    for mod, handle in ((A, A.AuditHandle(net)), (F, F.FidelityHandle(net))):
+        rows, want = handle.rows(), mod.rows_of(plan, (3, 15, 15))
+        assert len(rows) == 70 > mod.ROWS_PER_LAUNCH and handle.store_size == 813 * mod.SLOTS * 8
+        assert [(r["layer"], r["C"], r["H"], r["W"], r["offset"]) for r in rows] == [(r["layer"], r["C"], r["H"], r["W"], r["offset"]) for r in want]
 
 
 def test_the_kernel_constants_are_the_modules():

@@ -80,6 +80,14 @@ def test_small_programs(case, batch):
         assert len(ws) == rig.net.num_layer
 
 
+def test_more_rows_than_one_launch_takes():
+    """70 store rows: tf2_audit_run deals them to two launches of the rows kernel (64 and 5 table rows)"""
+    t, q, model, x = case_inputs("long", 2)
+    got, rows = Rig(t, q, model, 2).check(x)
+    assert len(rows) == 70 > A.ROWS_PER_LAUNCH
+    assert got.shape[0] == 813 and (got[:, A.N] > 0).all()
+
+
 # ---- 7. SSD: L2Norm row, independent pooling row, dilated row, heads with C = 4 nb and 21 nb -----------------------------------------
 def test_ssd_program():
     t = cfg.ssd300_tables(width_div=4)

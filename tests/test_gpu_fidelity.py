@@ -147,6 +147,23 @@ def test_null_references_leave_their_rows_empty():
     np.testing.assert_array_equal(rig.cmp.store(), got)
 
 
+def test_more_rows_than_one_launch_takes():
+    """70 store rows: tf2_fid_run deals the 69 table rows to two launches (64 and 5); with rows 60 .. 68 not compared the 60 that are
+    left fit one launch, the others' records stay empty"""
+    t, q, model, x = case_inputs("long", 2)
+    rig = Rig(t, q, model, 2)
+    refs = rig.refs(x)
+    got, rows, _ = rig.check(x, refs)
+    assert len(rows) == 70 > F.ROWS_PER_LAUNCH and got.shape[0] == 813 and (got[:, F.N] > 0).all()
+    part, _, _ = rig.check(x, [None if 60 <= l <= 68 else r for l, r in enumerate(refs)])
+    for r in rows[1:]:
+        rec = slice(r["offset"] // 144, r["offset"] // 144 + r["C"])
+        if 60 <= r["layer"] <= 68:
+            assert not part[rec].any(), r
+        else:
+            np.testing.assert_array_equal(part[rec], got[rec], err_msg=str(r))
+
+
 def test_scale_exponents_from_minus_64_to_64():
     """Any integer Q in -64 .. 64: the comparator's scale table replaced by one whose rows run over the whole range (both ends in every
     row), the references built around the engine's own values, (v + noise) * 2^-Q, so that every channel has small and large errors"""

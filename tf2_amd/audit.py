@@ -17,6 +17,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import config as cfg
+from ._observe import DeviceObserver, Handle, described_rows
 from .preprocess import quant_input, trans_of
 
 SLOTS = 16
@@ -88,12 +89,7 @@ def reference_input_quant(images, q0: int) -> np.ndarray:
 
 def rows_of(plan, image_chw) -> List[dict]:
     """What tf2_audit_describe reports, from the plan alone (n_doubled is the packed image's business: None here)"""
-    c, h, w = (int(v) for v in image_chw)
-    rows, rec = [dict(layer=-1, C=c, H=h, W=w, offset=0, n_doubled=0)], c
-    for L in plan:
-        rows.append(dict(layer=L.index, C=L.N, H=1 if L.endpool else L.PH, W=1 if L.endpool else L.PW, offset=rec * SLOTS * 8, n_doubled=None))
-        rec += L.N
-    return rows
+    return described_rows(plan, image_chw, SLOTS)
 
 
 # ---- verdicts -----------------------------------------------------------------------------------------------------------------
@@ -208,37 +204,12 @@ def report(summ: Dict[int, dict], top: int = 10) -> str:
 
 
 # ---- the device -------------------------------------------------------------------------------------------------------------------
-class AuditHandle:
+class AuditHandle(Handle):
     """tf2_audit_create on a packed NetWork (no device needed): rows(), store_size"""
-
-    def __init__(self, network):
-        import ctypes as C
-        from . import _lib
-        self.net = network
-        h = C.c_void_p()
-        _lib.check(_lib.lib().tf2_audit_create(network._h, C.byref(h)))
-        self._h = h
-        self.store_size = int(_lib.lib().tf2_audit_store_size(h))
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            from . import _lib
-            _lib.lib().tf2_audit_destroy(h)
-            self._h = None
-
-    def rows(self) -> List[dict]:
-        """[{layer, C, H, W, offset (bytes), n_doubled}], row -1 first (tf2_audit_describe)"""
-        import ctypes as C
-        from . import _lib
-        cap = self.net.num_layer + 1
-        arr = (_lib.AuditRow * cap)()
-        n = C.c_int(0)
-        _lib.check(_lib.lib().tf2_audit_describe(self._h, arr, cap, C.byref(n)))
-        return [dict(layer=r.layer, C=r.C, H=r.H, W=r.W, offset=int(r.store_offset), n_doubled=r.n_doubled) for r in arr[:n.value]]
+    PREFIX, SLOTS = "audit", SLOTS
 
 
-class DeviceAuditor(AuditHandle):
+class DeviceAuditor(DeviceObserver, AuditHandle):
     """The audit of `network` (a NetWork, packed and bound) at one batch size: owns the handle, the keep_all workspace, the logits and the
     int64 store as torch tensors.
       observe(images)   one keep_all step and the audit of every row behind it, enqueued on the current stream, accumulating into the
@@ -250,40 +221,13 @@ class DeviceAuditor(AuditHandle):
     store=: the store tensor of another auditor of the same network -- auditors that run side by side on several streams are separate
     objects (one workspace each) and may accumulate into one store: the adds are atomic."""
 
-    def __init__(self, network, batch: int, store=None):
-        import torch
-        from . import _lib
-        super().__init__(network)
-        self.batch = int(batch)
-        dev = network.device
-        ws = int(_lib.lib().tf2_audit_workspace_size(self._h, self.batch))
-        self._ws = torch.empty(max(ws, 256), dtype=torch.uint8, device=dev)
-        nbytes = int(_lib.lib().tf2_net_logits_size(network._h, self.batch))
-        n_out = network.plan[-1].N
-        self._logits = torch.empty((self.batch, n_out) if nbytes == self.batch * n_out else (self.batch, nbytes // (self.batch * n_out), n_out),
-                                   dtype=torch.int8, device=dev)
-        if store is None:
-            self.store_dev = torch.empty(self.store_size // 8, dtype=torch.int64, device=dev)
-            self.reset()
-        else:
-            assert store.dtype == torch.int64 and store.numel() * 8 >= self.store_size and store.device == dev
-            self.store_dev = store
-
-    def reset(self) -> None:
-        import torch
-        from . import _lib
-        stream = torch.cuda.current_stream(self.net.device).cuda_stream
-        _lib.check(_lib.lib().tf2_audit_store_init(self._h, self.store_dev.data_ptr(), self.store_dev.numel() * 8, stream))
-
     def observe(self, images):
         import torch
         from . import _lib
-        assert images.is_contiguous() and images.device == self.net.device and images.dtype in (torch.float32, torch.int8)
-        assert images.shape[0] == self.batch, (images.shape, self.batch)
-        stream = torch.cuda.current_stream(self.net.device).cuda_stream
+        self._check_images(images)
         _lib.check(_lib.lib().tf2_audit_run(self._h, images.data_ptr(), int(images.dtype == torch.int8), self.batch, self._ws.data_ptr(),
                                             self._ws.numel(), self._logits.data_ptr(), self.store_dev.data_ptr(), self.store_dev.numel() * 8,
-                                            stream))
+                                            self._stream()))
         return self._logits
 
     def audit_kept(self, images) -> None:
@@ -291,29 +235,11 @@ class DeviceAuditor(AuditHandle):
         once more.  `images` must be the batch that step received."""
         import torch
         from . import _lib
-        assert images.is_contiguous() and images.device == self.net.device and images.shape[0] == self.batch
-        stream = torch.cuda.current_stream(self.net.device).cuda_stream
+        self._check_images(images, typed=False)
         _lib.check(_lib.lib().tf2_audit_kept(self._h, images.data_ptr(), int(images.dtype == torch.int8), self.batch, self._ws.data_ptr(),
-                                             self._ws.numel(), self.store_dev.data_ptr(), self.store_dev.numel() * 8, stream))
+                                             self._ws.numel(), self.store_dev.data_ptr(), self.store_dev.numel() * 8, self._stream()))
 
     def capture(self, images, kept_only: bool = False):
         """kept_only: capture audit_kept(images) instead of observe(images)"""
-        import torch
-        dev = self.net.device
         step = (lambda: self.audit_kept(images)) if kept_only else (lambda: self.observe(images))
-        keep = self.store_dev.clone()
-        self.observe(images)                        # warm-up outside the capture; the store is put back
-        self.store_dev.copy_(keep)
-        torch.cuda.synchronize(dev)
-        g = torch.cuda.CUDAGraph()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            with torch.cuda.graph(g, stream=side):
-                step()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        self._graph = g
-        return g.replay
-
-    def store(self) -> np.ndarray:
-        return self.store_dev.cpu().numpy()[:self.store_size // 8].reshape(-1, SLOTS).copy()
+        return self._capture(step, lambda: self.observe(images))        # warm-up outside the capture; the store is put back

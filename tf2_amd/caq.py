@@ -35,6 +35,7 @@ from typing import Dict, List
 import numpy as np
 
 from . import config as cfg
+from ._observe import capture_graph, checked_refs, keeping, listed, store_rows
 
 RANGE_SLOTS = 70                     # kCaqRangeSlots
 ERROR_SLOTS = 12                     # kCaqErrorSlots
@@ -144,27 +145,19 @@ def error_records(x, qb) -> np.ndarray:
     return rec
 
 
-def _listed(x, n=None):
-    if isinstance(x, dict):
-        keys = sorted(k for k in x if k >= 0)
-        n = (keys[-1] + 1 if keys else 0) if n is None else n
-        return [x.get(l) for l in range(n)]
-    return list(x)
-
-
 def reference_range(maps, images=None) -> np.ndarray:
     """The RANGE store [records, 70] int64 of one observed batch.  maps: the rows' float32 maps in table order, [B][C][H][W] or [B][C]
     -- a sequence, or a dict {row: map} (its key -1 is not used).  images: the float32 images [B, C, H, W], whose channels lead the
     store; None: the input's records are left out."""
     parts = [] if images is None else [range_records(np.asarray(images, np.float32))]
-    parts += [range_records(np.asarray(m, np.float32)) for m in _listed(maps)]
+    parts += [range_records(np.asarray(m, np.float32)) for m in listed(maps)]
     return np.concatenate(parts, axis=0)
 
 
 def reference_error(maps, images, qb) -> np.ndarray:
     """The ERROR store [records, 12] int64 of one observed batch against qb [records], one base exponent a record in the store's order
     (the images' channels first unless images is None)"""
-    tensors = ([] if images is None else [np.asarray(images, np.float32)]) + [np.asarray(m, np.float32) for m in _listed(maps)]
+    tensors = ([] if images is None else [np.asarray(images, np.float32)]) + [np.asarray(m, np.float32) for m in listed(maps)]
     qb = np.asarray(qb, np.int64).reshape(-1)
     parts, at = [], 0
     for x in tensors:
@@ -255,12 +248,7 @@ def q_file_text(tables, rows: Dict[int, np.ndarray]) -> str:
 # ---- the device -------------------------------------------------------------------------------------------------------------------
 def rows_of(plan, image_chw) -> List[dict]:
     """[{layer, C, HW, first}] of the store, row -1 first"""
-    c, h, w = (int(v) for v in image_chw)
-    rows, at = [dict(layer=-1, C=c, HW=h * w, first=0)], c
-    for L in plan:
-        rows.append(dict(layer=L.index, C=int(L.N), HW=1 if L.endpool else int(L.PH) * int(L.PW), first=at))
-        at += int(L.N)
-    return rows
+    return [dict(layer=r["layer"], C=r["C"], HW=r["H"] * r["W"], first=r["first"]) for r in store_rows(plan, image_chw)]
 
 
 class DeviceCalibrator:
@@ -321,25 +309,14 @@ class DeviceCalibrator:
 
     def _tables(self, images, refs):
         """the host arrays tf2_caq_* read at enqueue (and the batch); every tensor checked against its row"""
-        import ctypes as C
-        import torch
         from . import _lib
-        nl = len(self.plan)
-        refs = _listed(refs, nl) if isinstance(refs, dict) else list(refs)
-        assert len(refs) == nl, (len(refs), nl)
-        tensors = [images] + refs
+        tensors = [images] + listed(refs, len(self.plan))
         batch = next((int(t.shape[0]) for t in tensors if t is not None), 0)
-        desc = (_lib.CaqRow * (nl + 1))()
-        ptrs = (C.c_void_p * (nl + 1))()
-        for i, (r, t) in enumerate(zip(self.rows, tensors)):
-            desc[i].C, desc[i].HW, desc[i].first_record = r["C"], r["HW"], r["first"]
-            if t is None:
-                ptrs[i] = None
-                continue
-            assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device, (r["layer"], t.dtype, t.device)
-            assert t.shape[0] == batch and t.shape[1] == r["C"] and t.numel() == batch * r["C"] * r["HW"], (r, tuple(t.shape))
-            ptrs[i] = t.data_ptr()
-        return desc, ptrs, nl + 1, batch
+        ptrs = checked_refs(self.rows, tensors, batch, self.device)
+        desc = (_lib.CaqRow * len(self.rows))()
+        for d, r in zip(desc, self.rows):
+            d.C, d.HW, d.first_record = r["C"], r["HW"], r["first"]
+        return desc, ptrs, len(self.rows), batch
 
     def observe(self, images, refs) -> None:
         from . import _lib
@@ -354,22 +331,10 @@ class DeviceCalibrator:
 
     def capture(self, images, refs, error: bool = False):
         """observe(images, refs) -- error=True: observe_error -- as a HIP graph: refill the buffers, replay"""
-        import torch
         step = (lambda: self.observe_error(images, refs)) if error else (lambda: self.observe(images, refs))
-        store = self.error_dev if error else self.range_dev
-        keep = store.clone()
-        step()                                      # warm-up outside the capture; the store is put back
-        store.copy_(keep)
-        torch.cuda.synchronize(self.device)
-        g = torch.cuda.CUDAGraph()
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):
-            with torch.cuda.graph(g, stream=side):
-                step()
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        self._graph = g
-        return g.replay
+        # warm-up outside the capture; the store is put back
+        self._graph = capture_graph(step, self.device, keeping(self.error_dev if error else self.range_dev, step))
+        return self._graph.replay
 
     def range_store(self) -> np.ndarray:
         return self.range_dev.cpu().numpy()[:self.records * RANGE_SLOTS].reshape(-1, RANGE_SLOTS).copy()

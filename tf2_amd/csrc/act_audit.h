@@ -1,7 +1,8 @@
 // act_audit.h -- the activation audit behind tf2_audit_* (include/tf2_amd.h): the handle (host) and the argument blocks of its kernels
 // (act_audit.hip).  tf2_amd/audit.py states the statistics (reference_audit); the device store equals it as integers.
 #pragma once
-#include "tf2_net.h"
+#include <cstddef>
+#include "act_rows.h"
 
 namespace tf2 {
 
@@ -27,6 +28,7 @@ struct AuditRowsArgs {
   AuditRow rows[kAuditRowsPerLaunch];
   int32_t n_rows;
 };
+static_assert(sizeof(AuditRow) == 56 && offsetof(AuditRowsArgs, n_rows) == 3584 && sizeof(AuditRowsArgs) == 3592, "the kernel's argument layout");
 
 // The input record: dense NCHW images, float32 (quantised with trans = 2^Q0 by quant_input) or int8.
 struct AuditImgArgs {
@@ -37,20 +39,14 @@ struct AuditImgArgs {
   int32_t slabs;             // blocks a plane
   int32_t vec;               // hw % 4 == 0 and an aligned base: a lane's four values are one 16-byte (float) or 4-byte (int8) load
 };
-
-int launch_audit_rows(const AuditRowsArgs& a, int blocks, void* stream);
-int launch_audit_image(const AuditImgArgs& a, void* stream);
-int launch_audit_init(long long* store, long long n_records, void* stream);
+static_assert(offsetof(AuditImgArgs, store) == 8 && offsetof(AuditImgArgs, vec) == 40 && sizeof(AuditImgArgs) == 48, "the kernel's argument layout");
 
 struct Auditor {
-  struct Row { int layer, C, H, W; long long rec0; int n_doubled; };
-  Net* net = nullptr;
-  std::vector<Row> rows;     // row -1 first
-  long long n_records = 0;
+  ActRows g;                 // the rows and their records (act_rows.h)
 
-  tf2_status create(Net* n);
-  size_t store_size() const { return (size_t)n_records * kAuditSlots * sizeof(long long); }
-  size_t workspace_size(int batch);
+  tf2_status create(Net* n) { return g.create(n); }
+  size_t store_size() const { return g.store_size(kAuditSlots); }
+  size_t workspace_size(int batch) { return g.workspace_size(batch); }
   tf2_status store_init(void* store, size_t store_bytes, void* stream) const;
   tf2_status run(const void* images, bool images_are_q, int batch, void* ws, size_t ws_bytes, int8_t* logits, void* store,
                  size_t store_bytes, void* stream, bool with_step = true);

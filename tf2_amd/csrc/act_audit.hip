@@ -1,7 +1,9 @@
 // act_audit.hip -- the activation audit (tf2_audit_*, include/tf2_amd.h): every kept map of a keep_all step reduced to exact per-channel
 // integer statistics in a caller-owned device store, with no host copy and no synchronisation.  tf2_amd/audit.py states the record
 // (reference_audit); the store equals it as integers, whatever the grid and the order of the blocks: every counter is an integer added
-// (or minimised / maximised) with a 64-bit atomic.
+// (or minimised / maximised) with a 64-bit atomic.  act_rows.h holds what this file shares with act_fidelity and act_caq: the rows of
+// a net (ActRows), the refusals and kept maps in front of Auditor::run (KeptMaps), the rows dealt to launches (LaunchBatch), the
+// block-to-row search, add64 and the wave reductions.
 //
 // The arithmetic is on four values of ONE channel packed in a dword (acc_dword): sum and sum of squares are one sdot4 each, the counts
 // are byte-parallel bit tricks closed by a population count -- negative = the sign bits; |v| per byte is (v ^ s) + sign with s = 0xff on
@@ -80,10 +82,6 @@ __device__ __forceinline__ void acc_dword(Acc& a, uint32_t t, uint32_t m) {
   for (int k = 0; k < 7; k++) a.ge[k] += __popc(sm & (0x01010101u << k));
 }
 
-__device__ __forceinline__ void add64(unsigned long long* p, long long v) {
-  if (v) atomicAdd(p, (unsigned long long)v);
-}
-
 // a channel's record from a block's (or a wave's) counters over n values
 __device__ __forceinline__ void flush_record(long long* rec, int n, int neg, int lo, int hi, int mn, int mx, int sum, int sq, const int (&ge)[7]) {
   unsigned long long* const u = reinterpret_cast<unsigned long long*>(rec);
@@ -143,9 +141,8 @@ __device__ __forceinline__ void walk_slab(Acc (&a)[4], const bool (&dbl)[4], con
 
 __global__ __launch_bounds__(kThreads) void audit_rows_kernel(AuditRowsArgs p) {
   __shared__ int red[kRedSlots][kAuditChans];
-  int r = 0;
-  for (int i = 1; i < p.n_rows; i++)
-    if ((int)blockIdx.x >= p.rows[i].block0) r = i;                 // (block0 ascends; block-uniform)
+  int r;
+  TF2_ROW_OF_BLOCK(r, p);
   const AuditRow& R = p.rows[r];
   const int local = (int)blockIdx.x - R.block0;
   const int slab = local / R.n_cpass, cpass = local - slab * R.n_cpass;
@@ -201,12 +198,6 @@ __global__ __launch_bounds__(kThreads) void audit_rows_kernel(AuditRowsArgs p) {
   }
 }
 
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 __global__ __launch_bounds__(kThreads) void audit_image_kernel(AuditImgArgs p) {
   const int plane = (int)blockIdx.x / p.slabs, slab = (int)blockIdx.x - plane * p.slabs;
   const int ch = plane % p.c;
@@ -249,9 +240,7 @@ __global__ __launch_bounds__(kThreads) void audit_image_kernel(AuditImgArgs p) {
   int ge[7];
 #pragma unroll
   for (int b = 0; b < 7; b++) ge[b] = wave_sum((int)a.ge[b]);
-  int mn = a.mn, mx = a.mx;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { mn = min(mn, __shfl_xor(mn, o)); mx = max(mx, __shfl_xor(mx, o)); }
+  const int mn = wave_min(a.mn), mx = wave_max(a.mx);
   // the block's waves meet in LDS: every block of a channel adds to the same few words of the store, so one thread a block does
   __shared__ int part[kThreads / 64][16];
   const int wave = threadIdx.x >> 6;
@@ -285,93 +274,40 @@ __global__ __launch_bounds__(kThreads) void audit_init_kernel(long long* store, 
 
 }  // namespace
 
-int launch_audit_rows(const AuditRowsArgs& a, int blocks, void* stream) {
-  hipLaunchKernelGGL(audit_rows_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_audit_image(const AuditImgArgs& a, void* stream) {
-  hipLaunchKernelGGL(audit_image_kernel, dim3((unsigned)((long long)a.planes * a.slabs)), dim3(kThreads), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_audit_init(long long* store, long long n_records, void* stream) {
-  const long long words = n_records * kAuditSlots;
-  hipLaunchKernelGGL(audit_init_kernel, dim3((unsigned)((words + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, store, words);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
 // ---- the handle --------------------------------------------------------------------------------------------------------
-tf2_status Auditor::create(Net* n) {
-  if (!n->packed_valid) { set_error("tf2_audit_create: no packed image (tf2_net_pack / tf2_net_packed_adopt first)"); return TF2_ERR_STATE; }
-  net = n;
-  rows.clear();
-  rows.push_back(Row{-1, n->nd.image_c, n->nd.image_h, n->nd.image_w, 0, 0});
-  long long rec = n->nd.image_c;
-  for (int l = 0; l < n->nd.n_layers; l++) {
-    const tf2_layer_desc& L = n->layers[l];
-    const PackLayer* pl = n->pack_layer(l);
-    const uint8_t* f = (pl && pl->off_dbl) ? n->packed.data() + pl->off_dbl : nullptr;
-    int nd = 0;
-    for (int c = 0; f && c < L.N; c++) nd += f[c] ? 1 : 0;
-    rows.push_back(Row{l, L.N, L.endpool ? 1 : L.PH, L.endpool ? 1 : L.PW, rec, nd});
-    rec += L.N;
-  }
-  n_records = rec;
-  return TF2_OK;
-}
-
-size_t Auditor::workspace_size(int batch) { return batch <= 0 ? 0 : net->workspace_size(batch, true); }
-
 tf2_status Auditor::store_init(void* store, size_t store_bytes, void* stream) const {
   if (!store) return arg_refusal("tf2_audit_store_init", "null store_dev");
   if (store_bytes < store_size()) { set_error("tf2_audit_store_init: store too small (tf2_audit_store_size: " + std::to_string(store_size()) + ")"); return TF2_ERR_SIZE; }
-  if (launch_audit_init((long long*)store, n_records, stream)) { set_error(std::string("tf2_audit_store_init: launch failed: ") + hipGetErrorString(hipGetLastError())); return TF2_ERR_HIP; }
-  return TF2_OK;
+  const long long words = g.n_records * kAuditSlots;
+  hipLaunchKernelGGL(audit_init_kernel, dim3((unsigned)((words + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, (long long*)store, words);
+  return launch_result("tf2_audit_store_init");
 }
 
 // with_step: the keep_all step first (tf2_audit_run); without, the audit alone of a workspace that holds one (tf2_audit_kept)
 tf2_status Auditor::run(const void* images, bool images_are_q, int batch, void* ws, size_t ws_bytes, int8_t* logits, void* store,
                         size_t store_bytes, void* stream, bool with_step) {
-  if (batch <= 0) return arg_refusal("tf2_audit_run", "batch must be positive");
-  if (!images || !ws || (with_step && !logits) || !store) return arg_refusal("tf2_audit_run", "null device pointer");
-  if (!net->packed_valid) { set_error("tf2_audit_run: no packed image (tf2_net_pack / tf2_net_packed_adopt)"); return TF2_ERR_STATE; }
-  if (!net->packed_dev) { set_error("tf2_audit_run: packed image not bound to the device (tf2_net_bind_device)"); return TF2_ERR_STATE; }
-  if ((int)rows.size() != net->nd.n_layers + 1) { set_error("tf2_audit_run: the handle does not fit the net"); return TF2_ERR_STATE; }
-  if (store_bytes < store_size()) { set_error("tf2_audit_run: store too small (tf2_audit_store_size: " + std::to_string(store_size()) + ")"); return TF2_ERR_SIZE; }
-  const WorkPlan* wp;
-  { std::lock_guard<std::mutex> lock(net->run_mutex); wp = net->plan(batch, true); }      // (map nodes are stable)
-  if (ws_bytes < wp->total_bytes) { set_error("tf2_audit_run: workspace too small (tf2_audit_workspace_size: " + std::to_string(wp->total_bytes) + ")"); return TF2_ERR_SIZE; }
+  Net* const net = g.net;
+  KeptMaps kept;
+  if (tf2_status st = kept.open(g, "tf2_audit", !images || !ws || (with_step && !logits) || !store, "null device pointer", batch, ws, ws_bytes,
+                                store_bytes, store_size(), 0))
+    return st;
   // every row and the grids, before anything is enqueued
-  const int nl = net->nd.n_layers;
-  std::vector<AuditRowsArgs> launches;
-  std::vector<int> blocks;
-  for (int l = 0; l < nl; l++) {
-    const LayerExec& E = wp->exec[l];
-    const TensorPlan& t = wp->tensors[E.out_tensor];
-    const Row& row = rows[l + 1];
-    const long long npix = (long long)batch * t.H * t.W;
-    if (t.H * t.W != row.H * row.W || E.out_off + row.C > t.Cp || npix > 0x7fffffffll) {
-      set_error("tf2_audit_run: row " + std::to_string(l) + ": the kept tensor does not have the row's shape"); return TF2_ERR_UNSUPPORTED;
-    }
-    if (launches.empty() || launches.back().n_rows == kAuditRowsPerLaunch) { launches.emplace_back(); launches.back().n_rows = 0; blocks.push_back(0); }
-    AuditRowsArgs& A = launches.back();
-    AuditRow& R = A.rows[A.n_rows++];
-    const PackLayer* pl = net->pack_layer(l);
-    R.base = (const int8_t*)ws + t.offset + E.out_off;
-    R.dbl = (pl && pl->off_dbl) ? net->packed_dev + pl->off_dbl : nullptr;
-    R.store = (long long*)store + row.rec0 * kAuditSlots;
-    R.npix = (int32_t)npix; R.c = row.C; R.cp = t.Cp;
-    R.block0 = blocks.back();
-    R.n_cpass = (row.C + kAuditChans - 1) / kAuditChans;
-    const int groups = (std::min(row.C, kAuditChans) + 3) / 4;
-    R.lp_shift = 0;
-    while ((1 << R.lp_shift) < groups) R.lp_shift++;
-    R.vec = (((uintptr_t)R.base & 3) == 0 && t.Cp % 4 == 0 && E.out_off + round_up(row.C, 4) <= t.Cp) ? 1 : 0;
-    R.pad = 0;
-    const long long nb = (npix + kAuditSlab - 1) / kAuditSlab * R.n_cpass;
-    if (blocks.back() + nb > 0x7fffffffll) { set_error("tf2_audit_run: too many blocks for one grid"); return TF2_ERR_UNSUPPORTED; }
-    blocks.back() += (int)nb;
+  LaunchBatch<AuditRowsArgs, AuditRow, kAuditRowsPerLaunch> rows("tf2_audit_run", AuditRowsArgs{});
+  for (int l = 0; l < net->nd.n_layers; l++) {
+    KeptMap m;
+    if (tf2_status st = kept.map(l, m)) return st;
+    const int n_cpass = (m.C + kAuditChans - 1) / kAuditChans;
+    AuditRow* const R = rows.add((m.npix + kAuditSlab - 1) / kAuditSlab * n_cpass);
+    if (!R) return TF2_ERR_UNSUPPORTED;
+    R->base = m.base; R->dbl = m.dbl;
+    R->store = (long long*)store + m.rec0 * kAuditSlots;
+    R->npix = (int32_t)m.npix; R->c = m.C; R->cp = m.Cp;
+    R->n_cpass = n_cpass;
+    const int groups = (std::min(m.C, kAuditChans) + 3) / 4;
+    R->lp_shift = 0;
+    while ((1 << R->lp_shift) < groups) R->lp_shift++;
+    R->vec = (((uintptr_t)m.base & 3) == 0 && m.Cp % 4 == 0 && m.off + round_up(m.C, 4) <= m.Cp) ? 1 : 0;
+    R->pad = 0;
   }
   AuditImgArgs I{};
   I.images = images; I.store = (long long*)store; I.trans = std::ldexp(1.0f, -(int)net->q[0]); I.is_q = images_are_q ? 1 : 0;
@@ -381,9 +317,12 @@ tf2_status Auditor::run(const void* images, bool images_are_q, int batch, void* 
 
   if (with_step)
     if (tf2_status st = net->run(images, images_are_q, batch, ws, ws_bytes, logits, stream)) return st;
-  if (launch_audit_image(I, stream)) { set_error(std::string("tf2_audit_run: image audit launch failed: ") + hipGetErrorString(hipGetLastError())); return TF2_ERR_HIP; }
-  for (size_t i = 0; i < launches.size(); i++)
-    if (launch_audit_rows(launches[i], blocks[i], stream)) { set_error(std::string("tf2_audit_run: audit launch failed: ") + hipGetErrorString(hipGetLastError())); return TF2_ERR_HIP; }
+  hipLaunchKernelGGL(audit_image_kernel, dim3((unsigned)((long long)I.planes * I.slabs)), dim3(kThreads), 0, (hipStream_t)stream, I);
+  if (tf2_status st = launch_result("tf2_audit_run", "image audit launch failed")) return st;
+  for (size_t i = 0; i < rows.launches.size(); i++) {
+    hipLaunchKernelGGL(audit_rows_kernel, dim3((unsigned)rows.blocks[i]), dim3(kThreads), 0, (hipStream_t)stream, rows.launches[i]);
+    if (tf2_status st = launch_result("tf2_audit_run", "audit launch failed")) return st;
+  }
   return TF2_OK;
 }
 

@@ -10,7 +10,8 @@
 // clamps to fit = 31) whatever the flush mode.  In the ERROR pass, with |Qb| <= 64 the scale is at most 2^71: a denormal input
 // (< 2^-126) or a denormal product gives |t| < 0.5 and e = 0 whether the multiplication flushes or not.
 #pragma once
-#include "tf2_net.h"
+#include <cstddef>
+#include "act_rows.h"
 
 namespace tf2 {
 
@@ -39,6 +40,8 @@ struct CaqArgs {
   const float* scales;       // ERROR pass: [records] 2^(Qb + 7); null in the RANGE pass
   int32_t n_rows;
 };
+static_assert(sizeof(CaqRow) == 32 && offsetof(CaqArgs, store) == 2048 && offsetof(CaqArgs, scales) == 2056 && offsetof(CaqArgs, n_rows) == 2064 &&
+              sizeof(CaqArgs) == 2072, "the kernel's argument layout");
 
 inline size_t caq_range_store_size(long long n_records) { return (size_t)n_records * kCaqRangeSlots * sizeof(long long); }
 inline size_t caq_error_store_size(long long n_records) { return (size_t)n_records * kCaqErrorSlots * sizeof(long long); }

@@ -1,7 +1,8 @@
 // act_caq.hip -- CAQ calibration (tf2_caq_*, include/tf2_amd.h): the float32 maps of a float forward, read once, into exact per-channel
 // integer records in a caller-owned device store, with no host copy and no synchronisation.  tf2_amd/caq.py states both records
 // (reference_range / reference_error); the stores equal it as integers, whatever the grid and the order of the blocks: every counter
-// is an integer added (or maximised) with a 64-bit atomic.
+// is an integer added (or maximised) with a 64-bit atomic.  act_rows.h holds what this file shares with act_audit and act_fidelity: the
+// rows dealt to launches (LaunchBatch), the block-to-row search, add64 and the wave reductions.
 //
 // caq_range_kernel   pass 1.  Per value, on the bit pattern (mag = bits & 0x7fffffff): mag >= 0x7f800000 -> nonfinite, nothing else;
 //                    mag == 0 -> zeros; otherwise the sign picks negatives and the peak it may raise, and the value falls into
@@ -48,26 +49,6 @@ constexpr int kWaves = kThreads / 64;
 static_assert(kCaqSlab % (kWaves * kCaqGroup) == 0 && kCaqGroup == 4, "a wave's share of a whole slab is whole groups of four");
 static_assert(kCaqSlab / kWaves / 64 * 8 <= 1024, "a lane sees at most 2^10 values: a 64th of its wave's share, a few times that where planes are short");
 static_assert(kCaqBins == 64, "a lane a bin");
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor(v, o));
-  return v;
-}
-
-__device__ __forceinline__ void add64(long long* p, unsigned long long v) {
-  if (v) atomicAdd(reinterpret_cast<unsigned long long*>(p), v);
-}
 
 // The values [wv0, wv1) of channel c of row R (a channel's values in (b, i) order: v = b * hw + i), every one handed to acc.count(bits,
 // true) exactly once; the calls are made by all 64 lanes together (acc.count may use wave-wide operations), a lane without a value
@@ -118,9 +99,7 @@ struct Share {
 };
 __device__ __forceinline__ Share share_of(const CaqArgs& p, int wave) {
   Share s;
-  s.r = 0;
-  for (int i = 1; i < p.n_rows; i++)
-    if ((int)blockIdx.x >= p.rows[i].block0) s.r = i;               // (block0 ascends; block-uniform)
+  TF2_ROW_OF_BLOCK(s.r, p);
   const CaqRow& R = p.rows[s.r];
   const int local = (int)blockIdx.x - R.block0;
   const int slab = local / R.c;
@@ -299,29 +278,23 @@ tf2_status caq_run(bool error, const tf2_caq_row* rows, const void* const* maps,
     set_error(who + "store too small: the rows reach record " + std::to_string(last) + ", store_bytes holds " + std::to_string(capacity));
     return TF2_ERR_SIZE;
   }
-  std::vector<CaqArgs> launches;
-  std::vector<long long> blocks;
+  CaqArgs first{};
+  first.store = (long long*)store; first.scales = error ? scales_dev : nullptr;
+  LaunchBatch<CaqArgs, CaqRow, kCaqRowsPerLaunch> batches(error ? "tf2_caq_error" : "tf2_caq_range", first);
   for (int i = 0; i < n_rows; i++) {
     if (!maps[i]) continue;                                          // not observed: no block, its records stay
-    if (launches.empty() || launches.back().n_rows == kCaqRowsPerLaunch) {
-      launches.emplace_back();
-      launches.back().n_rows = 0; launches.back().store = (long long*)store; launches.back().scales = error ? scales_dev : nullptr;
-      blocks.push_back(0);
-    }
-    CaqArgs& A = launches.back();
-    CaqRow& R = A.rows[A.n_rows++];
-    R.map = (const uint32_t*)maps[i];
-    R.c = rows[i].C; R.hw = rows[i].HW; R.total = batch * rows[i].HW;
-    R.n_slabs = (R.total + kCaqSlab - 1) / kCaqSlab;
-    R.block0 = (int32_t)blocks.back();
-    R.rec0 = (int32_t)rows[i].first_record;
-    blocks.back() += (long long)R.n_slabs * R.c;
-    if (blocks.back() > 0x7fffffffll) { set_error(who + "too many blocks for one grid"); return TF2_ERR_UNSUPPORTED; }
+    const int total = batch * rows[i].HW, n_slabs = (total + kCaqSlab - 1) / kCaqSlab;
+    CaqRow* const R = batches.add((long long)n_slabs * rows[i].C);
+    if (!R) return TF2_ERR_UNSUPPORTED;
+    R->map = (const uint32_t*)maps[i];
+    R->c = rows[i].C; R->hw = rows[i].HW; R->total = total;
+    R->n_slabs = n_slabs;
+    R->rec0 = (int32_t)rows[i].first_record;
   }
-  for (size_t i = 0; i < launches.size(); i++) {
-    if (error) hipLaunchKernelGGL(caq_error_kernel, dim3((unsigned)blocks[i]), dim3(kThreads), 0, (hipStream_t)stream, launches[i]);
-    else hipLaunchKernelGGL(caq_range_kernel, dim3((unsigned)blocks[i]), dim3(kThreads), 0, (hipStream_t)stream, launches[i]);
-    if (hipGetLastError() != hipSuccess) { set_error(who + "launch failed: " + hipGetErrorString(hipGetLastError())); return TF2_ERR_HIP; }
+  for (size_t i = 0; i < batches.launches.size(); i++) {
+    if (error) hipLaunchKernelGGL(caq_error_kernel, dim3((unsigned)batches.blocks[i]), dim3(kThreads), 0, (hipStream_t)stream, batches.launches[i]);
+    else hipLaunchKernelGGL(caq_range_kernel, dim3((unsigned)batches.blocks[i]), dim3(kThreads), 0, (hipStream_t)stream, batches.launches[i]);
+    if (tf2_status st = launch_result(batches.fn.c_str())) return st;
   }
   return TF2_OK;
 }

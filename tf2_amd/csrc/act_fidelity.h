@@ -7,7 +7,8 @@
 // kernel), a block kFidSlab a channel: every partial sum but sum_d2 and sum_e2 fits 32 bits (sum_abs_d < 2^10 * 2^17), and the seven
 // 9-bit fields of a thread's packed histogram hold 511 each.
 #pragma once
-#include "act_audit.h"
+#include <cstddef>
+#include "act_rows.h"
 
 namespace tf2 {
 
@@ -35,6 +36,8 @@ struct FidRowsArgs {
   const float* scales;       // [records]: 2^(Q + 8) of every channel
   int32_t n_rows;
 };
+static_assert(sizeof(FidRow) == 48 && offsetof(FidRowsArgs, store) == 3072 && offsetof(FidRowsArgs, scales) == 3080 &&
+              offsetof(FidRowsArgs, n_rows) == 3088 && sizeof(FidRowsArgs) == 3096, "the kernel's argument layout");
 
 // The input record: dense NCHW float32 images against their own quantisation (quant_input with trans = 2^Q0).
 struct FidImgArgs {
@@ -44,18 +47,15 @@ struct FidImgArgs {
   int32_t c, hw, planes;     // planes = batch * c
   int32_t slabs;             // blocks a plane
 };
-
-int launch_fid_rows(const FidRowsArgs& a, int blocks, void* stream);
-int launch_fid_image(const FidImgArgs& a, void* stream);
+static_assert(offsetof(FidImgArgs, store) == 8 && offsetof(FidImgArgs, slabs) == 36 && sizeof(FidImgArgs) == 40, "the kernel's argument layout");
 
 struct Comparator {
-  Auditor aud;               // the rows and their records: the audit's geometry
-  Net* net = nullptr;
+  ActRows g;                 // the rows and their records (act_rows.h)
   std::vector<float> scale;  // [records]: 2^(Q + 8); a pooling row's Q is its source's (the runtime table already says so)
 
   tf2_status create(Net* n);
-  size_t store_size() const { return (size_t)aud.n_records * kFidSlots * sizeof(long long); }
-  size_t workspace_size(int batch) { return aud.workspace_size(batch); }
+  size_t store_size() const { return g.store_size(kFidSlots); }
+  size_t workspace_size(int batch) { return g.workspace_size(batch); }
   tf2_status store_init(void* store, size_t store_bytes, void* stream) const;
   tf2_status run(const void* images, bool images_are_q, int batch, void* ws, size_t ws_bytes, int8_t* logits, void* store,
                  size_t store_bytes, const float* const* refs, const float* scales_dev, void* stream, bool with_step = true);

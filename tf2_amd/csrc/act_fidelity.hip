@@ -1,7 +1,9 @@
 // act_fidelity.hip -- layer fidelity (tf2_fid_*, include/tf2_amd.h): every kept int8 map of a keep_all step set against the float32 map of
 // a float forward, per channel, in a caller-owned device store, with no host copy and no synchronisation.  tf2_amd/fidelity.py states
 // the record (reference_compare); the store equals it as integers, whatever the grid and the order of the blocks: every counter is an
-// integer added (or maximised) with a 64-bit atomic.
+// integer added (or maximised) with a 64-bit atomic.  act_rows.h holds what this file shares with act_audit and act_caq: the rows of a
+// net (ActRows), the refusals and kept maps in front of Comparator::run (KeptMaps), the rows dealt to launches (LaunchBatch), the
+// block-to-row search, add64 and the wave reductions.
 //
 // Per value (fid_count): f not finite -> nonfinite, nothing else.  t = f * 2^(Q + 8), one float32 multiplication; |t| >= 65536 (an
 // overflow to inf included) -> e = +-65536 and ref_clamped; else e = rint(t), half to even.  d = 256 v - e, |d| < 2^17;
@@ -121,10 +123,6 @@ __device__ __forceinline__ void red_add(Red& R, int ch, const Acc& a, int valid)
   if (a.e2) atomicAdd(&R.q[1][ch], a.e2);
 }
 
-__device__ __forceinline__ void add64(unsigned long long* p, long long v) {
-  if (v) atomicAdd(p, (unsigned long long)v);
-}
-
 // a channel's record from a block's counters
 __device__ __forceinline__ void flush_record(long long* rec, long long n, long long nonfin, long long clamp, long long maxd, long long sd,
                                              long long sad, unsigned long long d2, long long sae, unsigned long long e2, long long sv2,
@@ -162,9 +160,8 @@ __device__ __forceinline__ float4 load_ref4(const float* ref, bool aligned, uint
 __global__ __launch_bounds__(kThreads) void fid_rows_kernel(FidRowsArgs p) {
   __shared__ float tile[2][kFidChans * kPitch];
   __shared__ Red red;
-  int r = 0;
-  for (int i = 1; i < p.n_rows; i++)
-    if ((int)blockIdx.x >= p.rows[i].block0) r = i;                 // (block0 ascends; block-uniform)
+  int r;
+  TF2_ROW_OF_BLOCK(r, p);
   const FidRow& R = p.rows[r];
   const int C = R.c, cp = R.cp;
   const uint32_t hw = (uint32_t)R.hw;
@@ -272,14 +269,10 @@ __global__ __launch_bounds__(kThreads) void fid_image_kernel(FidImgArgs p) {
     long long w[kRed32];
 #pragma unroll
     for (int s = 0; s < kRed32; s++) {
-      int v = red.w[s][lane];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) { const int u = __shfl_xor(v, o); v = s == 3 ? max(v, u) : v + u; }
+      const int v = s == 3 ? wave_max(red.w[s][lane]) : wave_sum(red.w[s][lane]);
       w[s] = s == 5 || s == 6 || s == 7 ? (long long)(uint32_t)v : (long long)v;
     }
-    unsigned long long d2 = red.q[0][lane], e2 = red.q[1][lane];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { d2 += __shfl_xor(d2, o); e2 += __shfl_xor(e2, o); }
+    const unsigned long long d2 = wave_sum(red.q[0][lane]), e2 = wave_sum(red.q[1][lane]);
     if (lane == 0) {
       const long long h[7] = {w[8], w[9], w[10], w[11], w[12], w[13], w[14]};
       flush_record(p.store + (long long)ch * kFidSlots, w[0], w[1], w[2], w[3], w[4], w[5], d2, w[6], e2, w[7], h);
@@ -289,24 +282,13 @@ __global__ __launch_bounds__(kThreads) void fid_image_kernel(FidImgArgs p) {
 
 }  // namespace
 
-int launch_fid_rows(const FidRowsArgs& a, int blocks, void* stream) {
-  hipLaunchKernelGGL(fid_rows_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_fid_image(const FidImgArgs& a, void* stream) {
-  hipLaunchKernelGGL(fid_image_kernel, dim3((unsigned)((long long)a.planes * a.slabs)), dim3(kThreads), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
 // ---- the handle --------------------------------------------------------------------------------------------------------
 tf2_status Comparator::create(Net* n) {
-  if (tf2_status st = aud.create(n)) return st;
+  if (tf2_status st = g.create(n)) return st;
   if (n->q.size() < (size_t)(n->nd.n_layers + 1) * n->nd.max_out_channel) { set_error("tf2_fid_create: q table not set (tf2_net_set_q first)"); return TF2_ERR_STATE; }
-  net = n;
-  scale.assign((size_t)aud.n_records, 0.0f);
+  scale.assign((size_t)g.n_records, 0.0f);
   const int M = n->nd.max_out_channel;
-  for (const Auditor::Row& row : aud.rows)
+  for (const ActRows::Row& row : g.rows)
     for (int c = 0; c < row.C; c++) {
       const int Q = -(int)(row.layer < 0 ? n->q[0] : n->q[(size_t)(row.layer + 1) * M + c]);     // Verify: 1 << -q[l + 1][c]; the input: q[0][0]
       if (Q + kFidFrac > 127 || Q + kFidFrac < -126) { set_error("tf2_fid_create: row " + std::to_string(row.layer) + ": 2^(Q + 8) is no normal float32"); return TF2_ERR_UNSUPPORTED; }
@@ -325,45 +307,25 @@ tf2_status Comparator::store_init(void* store, size_t store_bytes, void* stream)
 // with_step: the keep_all step first (tf2_fid_run); without, the comparison alone of a workspace that holds one (tf2_fid_kept)
 tf2_status Comparator::run(const void* images, bool images_are_q, int batch, void* ws, size_t ws_bytes, int8_t* logits, void* store,
                            size_t store_bytes, const float* const* refs, const float* scales_dev, void* stream, bool with_step) {
-  if (batch <= 0) return arg_refusal("tf2_fid_run", "batch must be positive");
-  if (!images || !ws || (with_step && !logits) || !store || !refs || !scales_dev) return arg_refusal("tf2_fid_run", "null pointer");
-  if (!net->packed_valid) { set_error("tf2_fid_run: no packed image (tf2_net_pack / tf2_net_packed_adopt)"); return TF2_ERR_STATE; }
-  if (!net->packed_dev) { set_error("tf2_fid_run: packed image not bound to the device (tf2_net_bind_device)"); return TF2_ERR_STATE; }
-  if ((int)aud.rows.size() != net->nd.n_layers + 1) { set_error("tf2_fid_run: the handle does not fit the net"); return TF2_ERR_STATE; }
-  if (store_bytes < store_size()) { set_error("tf2_fid_run: store too small (tf2_fid_store_size: " + std::to_string(store_size()) + ")"); return TF2_ERR_SIZE; }
-  const WorkPlan* wp;
-  { std::lock_guard<std::mutex> lock(net->run_mutex); wp = net->plan(batch, true); }      // (map nodes are stable)
-  if (ws_bytes < wp->total_bytes) { set_error("tf2_fid_run: workspace too small (tf2_fid_workspace_size: " + std::to_string(wp->total_bytes) + ")"); return TF2_ERR_SIZE; }
+  Net* const net = g.net;
+  KeptMaps kept;
+  if (tf2_status st = kept.open(g, "tf2_fid", !images || !ws || (with_step && !logits) || !store || !refs || !scales_dev, "null pointer", batch, ws,
+                                ws_bytes, store_bytes, store_size(), kFidSlab))
+    return st;
   // every row and the grids, before anything is enqueued
-  const int nl = net->nd.n_layers;
-  std::vector<FidRowsArgs> launches;
-  std::vector<int> blocks;
-  for (int l = 0; l < nl; l++) {
-    const LayerExec& E = wp->exec[l];
-    const TensorPlan& t = wp->tensors[E.out_tensor];
-    const Auditor::Row& row = aud.rows[l + 1];
-    const long long npix = (long long)batch * t.H * t.W;
-    if (t.H * t.W != row.H * row.W || E.out_off + row.C > t.Cp || npix + kFidSlab > 0x7fffffffll) {
-      set_error("tf2_fid_run: row " + std::to_string(l) + ": the kept tensor does not have the row's shape"); return TF2_ERR_UNSUPPORTED;
-    }
+  FidRowsArgs first{};
+  first.store = (long long*)store; first.scales = scales_dev;
+  LaunchBatch<FidRowsArgs, FidRow, kFidRowsPerLaunch> rows("tf2_fid_run", first);
+  for (int l = 0; l < net->nd.n_layers; l++) {
+    KeptMap m;
+    if (tf2_status st = kept.map(l, m)) return st;
     if (!refs[l]) continue;
-    if (launches.empty() || launches.back().n_rows == kFidRowsPerLaunch) {
-      launches.emplace_back();
-      launches.back().n_rows = 0; launches.back().store = (long long*)store; launches.back().scales = scales_dev;
-      blocks.push_back(0);
-    }
-    FidRowsArgs& A = launches.back();
-    FidRow& R = A.rows[A.n_rows++];
-    const PackLayer* pl = net->pack_layer(l);
-    R.base = (const int8_t*)ws + t.offset + E.out_off;
-    R.dbl = (pl && pl->off_dbl) ? net->packed_dev + pl->off_dbl : nullptr;
-    R.ref = refs[l];
-    R.npix = (int32_t)npix; R.c = row.C; R.cp = t.Cp; R.hw = row.H * row.W;
-    R.block0 = blocks.back();
-    R.rec0 = (int32_t)row.rec0;
-    const long long nb = (npix + kFidSlab - 1) / kFidSlab * ((row.C + kFidChans - 1) / kFidChans);
-    if (blocks.back() + nb > 0x7fffffffll) { set_error("tf2_fid_run: too many blocks for one grid"); return TF2_ERR_UNSUPPORTED; }
-    blocks.back() += (int)nb;
+    FidRow* const R = rows.add((m.npix + kFidSlab - 1) / kFidSlab * ((m.C + kFidChans - 1) / kFidChans));
+    if (!R) return TF2_ERR_UNSUPPORTED;
+    R->base = m.base; R->dbl = m.dbl;
+    R->ref = refs[l];
+    R->npix = (int32_t)m.npix; R->c = m.C; R->cp = m.Cp; R->hw = m.HW;
+    R->rec0 = (int32_t)m.rec0;
   }
   FidImgArgs I{};
   I.images = (const float*)images; I.store = (long long*)store; I.trans = std::ldexp(1.0f, -(int)net->q[0]); I.scale = scale[0];
@@ -372,10 +334,14 @@ tf2_status Comparator::run(const void* images, bool images_are_q, int batch, voi
 
   if (with_step)
     if (tf2_status st = net->run(images, images_are_q, batch, ws, ws_bytes, logits, stream)) return st;
-  if (!images_are_q)
-    if (launch_fid_image(I, stream)) { set_error(std::string("tf2_fid_run: input launch failed: ") + hipGetErrorString(hipGetLastError())); return TF2_ERR_HIP; }
-  for (size_t i = 0; i < launches.size(); i++)
-    if (launch_fid_rows(launches[i], blocks[i], stream)) { set_error(std::string("tf2_fid_run: launch failed: ") + hipGetErrorString(hipGetLastError())); return TF2_ERR_HIP; }
+  if (!images_are_q) {
+    hipLaunchKernelGGL(fid_image_kernel, dim3((unsigned)((long long)I.planes * I.slabs)), dim3(kThreads), 0, (hipStream_t)stream, I);
+    if (tf2_status st = launch_result("tf2_fid_run", "input launch failed")) return st;
+  }
+  for (size_t i = 0; i < rows.launches.size(); i++) {
+    hipLaunchKernelGGL(fid_rows_kernel, dim3((unsigned)rows.blocks[i]), dim3(kThreads), 0, (hipStream_t)stream, rows.launches[i]);
+    if (tf2_status st = launch_result("tf2_fid_run")) return st;
+  }
   return TF2_OK;
 }
 

@@ -34,6 +34,19 @@ struct tf2_fid { Comparator impl; };
 #define CHECK_NET(n)                                              \
   if (!(n)) { set_error("null tf2_net handle"); return TF2_ERR_ARG; }
 
+// tf2_audit_create / tf2_fid_create: a handle (its impl has create(Net*)) on a net, deleted again where create refuses
+template <class H>
+static tf2_status create_observer(const char* fn, tf2_net* net, H** out) {
+  CHECK_NET(net);
+  if (!out) return arg_refusal(fn, "null argument");
+  H* h = new (std::nothrow) H();
+  if (!h) { set_error("out of memory"); return TF2_ERR_SIZE; }
+  const tf2_status st = h->impl.create(&net->impl);
+  if (st != TF2_OK) { delete h; return st; }
+  *out = h;
+  return TF2_OK;
+}
+
 extern "C" {
 
 const char* tf2_last_error(void) { return last_error().c_str(); }
@@ -445,16 +458,7 @@ tf2_status tf2_emb_roc_pairs(const float* rows_dev, int n_rows, int d, const int
   return emb_roc_pairs(rows_dev, n_rows, d, pairs_dev, n_pairs, n_folds, n_thr, step, dist_dev, hist_dev, invalid_dev, stream);
 }
 
-tf2_status tf2_audit_create(tf2_net* net, tf2_audit** out) {
-  CHECK_NET(net);
-  if (!out) return arg_refusal("tf2_audit_create", "null argument");
-  tf2_audit* a = new (std::nothrow) tf2_audit();
-  if (!a) { set_error("out of memory"); return TF2_ERR_SIZE; }
-  const tf2_status st = a->impl.create(&net->impl);
-  if (st != TF2_OK) { delete a; return st; }
-  *out = a;
-  return TF2_OK;
-}
+tf2_status tf2_audit_create(tf2_net* net, tf2_audit** out) { return create_observer("tf2_audit_create", net, out); }
 
 void tf2_audit_destroy(tf2_audit* a) { delete a; }
 
@@ -462,16 +466,7 @@ size_t tf2_audit_store_size(const tf2_audit* a) { return a ? a->impl.store_size(
 
 tf2_status tf2_audit_describe(const tf2_audit* a, tf2_audit_row* rows, int capacity, int* n) {
   if (!a) { set_error("null tf2_audit handle"); return TF2_ERR_ARG; }
-  if (!n || (capacity > 0 && !rows)) return arg_refusal("tf2_audit_describe", "null argument");
-  const auto& v = a->impl.rows;
-  *n = (int)v.size();
-  if ((int)v.size() > capacity) { set_error("tf2_audit_describe: " + std::to_string(v.size()) + " rows, capacity " + std::to_string(capacity)); return TF2_ERR_SIZE; }
-  for (size_t i = 0; i < v.size(); i++) {
-    rows[i].layer = v[i].layer; rows[i].C = v[i].C; rows[i].H = v[i].H; rows[i].W = v[i].W;
-    rows[i].store_offset = (int64_t)(v[i].rec0 * kAuditSlots * 8);
-    rows[i].n_doubled = v[i].n_doubled; rows[i].reserved = 0;
-  }
-  return TF2_OK;
+  return a->impl.g.describe("tf2_audit_describe", kAuditSlots, rows, capacity, n);
 }
 
 tf2_status tf2_audit_store_init(const tf2_audit* a, void* store_dev, size_t store_bytes, void* hip_stream) {
@@ -493,16 +488,7 @@ tf2_status tf2_audit_kept(tf2_audit* a, const void* images_dev, int images_are_q
   return a->impl.run(images_dev, images_are_q != 0, batch, ws, ws_bytes, nullptr, store_dev, store_bytes, hip_stream, false);
 }
 
-tf2_status tf2_fid_create(tf2_net* net, tf2_fid** out) {
-  CHECK_NET(net);
-  if (!out) return arg_refusal("tf2_fid_create", "null argument");
-  tf2_fid* f = new (std::nothrow) tf2_fid();
-  if (!f) { set_error("out of memory"); return TF2_ERR_SIZE; }
-  const tf2_status st = f->impl.create(&net->impl);
-  if (st != TF2_OK) { delete f; return st; }
-  *out = f;
-  return TF2_OK;
-}
+tf2_status tf2_fid_create(tf2_net* net, tf2_fid** out) { return create_observer("tf2_fid_create", net, out); }
 
 void tf2_fid_destroy(tf2_fid* f) { delete f; }
 
@@ -510,16 +496,7 @@ size_t tf2_fid_store_size(const tf2_fid* f) { return f ? f->impl.store_size() : 
 
 tf2_status tf2_fid_describe(const tf2_fid* f, tf2_audit_row* rows, int capacity, int* n) {
   if (!f) { set_error("null tf2_fid handle"); return TF2_ERR_ARG; }
-  if (!n || (capacity > 0 && !rows)) return arg_refusal("tf2_fid_describe", "null argument");
-  const auto& v = f->impl.aud.rows;
-  *n = (int)v.size();
-  if ((int)v.size() > capacity) { set_error("tf2_fid_describe: " + std::to_string(v.size()) + " rows, capacity " + std::to_string(capacity)); return TF2_ERR_SIZE; }
-  for (size_t i = 0; i < v.size(); i++) {
-    rows[i].layer = v[i].layer; rows[i].C = v[i].C; rows[i].H = v[i].H; rows[i].W = v[i].W;
-    rows[i].store_offset = (int64_t)(v[i].rec0 * kFidSlots * 8);
-    rows[i].n_doubled = v[i].n_doubled; rows[i].reserved = 0;
-  }
-  return TF2_OK;
+  return f->impl.g.describe("tf2_fid_describe", kFidSlots, rows, capacity, n);
 }
 
 tf2_status tf2_fid_scales(const tf2_fid* f, float* scales, int capacity, int* n) {

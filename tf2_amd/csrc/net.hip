@@ -22,10 +22,10 @@ static thread_local std::string g_err;
 void set_error(const std::string& s) { g_err = s; }
 const std::string& last_error() { return g_err; }
 tf2_status arg_refusal(const char* fn, const std::string& what) { set_error(std::string(fn) + ": " + what); return TF2_ERR_ARG; }
-tf2_status launch_result(const char* fn) {
+tf2_status launch_result(const char* fn, const char* what) {
   const hipError_t e = hipGetLastError();
   if (e == hipSuccess) return TF2_OK;
-  set_error(std::string(fn) + ": launch failed: " + hipGetErrorString(e));
+  set_error(std::string(fn) + ": " + what + ": " + hipGetErrorString(e));
   return TF2_ERR_HIP;
 }
 

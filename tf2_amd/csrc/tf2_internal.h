@@ -499,9 +499,10 @@ struct Tensor {           // a device activation tensor [B][H][W][Cp]
 
 void set_error(const std::string& s);
 // how an entry point `fn` ("tf2_x") leaves: with a refused argument -- the error text becomes "tf2_x: " + what, TF2_ERR_ARG -- or with
-// the result of the launch it just made: TF2_OK, or "tf2_x: launch failed: " + the HIP error and TF2_ERR_HIP
+// the result of the launch it just made: TF2_OK, or "tf2_x: launch failed: " + the HIP error and TF2_ERR_HIP (what: another text than
+// "launch failed" where an entry point makes launches of several kinds)
 tf2_status arg_refusal(const char* fn, const std::string& what);
-tf2_status launch_result(const char* fn);
+tf2_status launch_result(const char* fn, const char* what = "launch failed");
 uint8_t get_real(float data, int8_t expand);
 
 }  // namespace tf2

@@ -35,6 +35,7 @@
 #include <cmath>
 #include <string>
 #include <vector>
+#include "act_rows.h"      // add64
 #include "weight_dnscp.h"
 
 namespace tf2 {
@@ -121,9 +122,6 @@ __device__ __forceinline__ unsigned long long wave_add64(unsigned long long v) {
   return v;
 }
 
-__device__ __forceinline__ void add64(long long* p, unsigned long long v) {
-  if (v) atomicAdd(reinterpret_cast<unsigned long long*>(p), v);
-}
 __device__ __forceinline__ void max64(long long* p, unsigned long long v) {
   if (v) atomicMax(reinterpret_cast<unsigned long long*>(p), v);
 }

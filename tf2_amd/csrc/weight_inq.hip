@@ -34,6 +34,7 @@
 #include <cmath>
 #include <string>
 #include <vector>
+#include "act_rows.h"      // add64
 #include "weight_inq.h"
 
 namespace tf2 {
@@ -109,9 +110,6 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
   return v;
 }
 
-__device__ __forceinline__ void add64(long long* p, unsigned long long v) {
-  if (v) atomicAdd(reinterpret_cast<unsigned long long*>(p), v);
-}
 __device__ __forceinline__ void max64(long long* p, unsigned long long v) {
   if (v) atomicMax(reinterpret_cast<unsigned long long*>(p), v);
 }

@@ -419,19 +419,10 @@ class DevicePruner:
     def capture(self, dense_dev, out_dev, update: Optional[Sequence[int]] = None):
         """A HIP graph of step(...) on these buffers.  The warm-up call outside the capture is a real step: it changes the keep bytes
         (and dense_dev where out_dev is dense_dev), so set them before every replay."""
-        import torch
-        dev = dense_dev.device
-        self.step(dense_dev, out_dev, update)                       # warm-up: buffers allocated, kernels loaded
-        torch.cuda.synchronize(dev)
-        g = torch.cuda.CUDAGraph()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            with torch.cuda.graph(g, stream=side):
-                self.step(dense_dev, out_dev, update)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        self._graph = g
-        return g.replay
+        from ._observe import capture_graph
+        # (the warm-up: buffers allocated, kernels loaded)
+        self._graph = capture_graph(lambda: self.step(dense_dev, out_dev, update), dense_dev.device)
+        return self._graph.replay
 
     def _split(self, flat) -> dict:
         return {i: flat[a:b].copy() for i, a, b in zip(self.ids, self.keep_off[:-1], self.keep_off[1:])}

@@ -26,6 +26,7 @@ from typing import Dict, List, Optional
 import numpy as np
 
 from . import calibrate
+from ._observe import DeviceObserver, Handle, checked_refs, described_rows, listed
 from .preprocess import quant_input
 
 SLOTS = 18
@@ -109,14 +110,6 @@ def channel_records(v, f, q) -> np.ndarray:
     return rec
 
 
-def _listed(x, n=None):
-    if isinstance(x, dict):
-        keys = sorted(k for k in x if k >= 0)
-        n = (keys[-1] + 1 if keys else 0) if n is None else n
-        return [x.get(l) for l in range(n)]
-    return list(x)
-
-
 def reference_compare(maps, refs, q_rows, images=None, q0=None) -> np.ndarray:
     """The store [records, 18] int64 of one compared batch.  maps: the rows' int8 outputs in table order, NCHW ([B][N] or [B][N][1][1] for
     an end-pool row) -- a sequence, or a dict {row: map} such as oracle.netref.RefNet.run returns (its key -1 is not used).  refs: the
@@ -124,8 +117,8 @@ def reference_compare(maps, refs, q_rows, images=None, q0=None) -> np.ndarray:
     row the channels' scale exponents Q (scale 2^Q; q_rows_of_net).  images, q0: the float32 images [B, C, H, W] the step received and
     the input's exponent Q0 -- row -1 leads the result, v = quant_input(images, 2^Q0) against the same floats; int8 images: a row of
     empty records; None: the input's records are left out."""
-    maps = _listed(maps)
-    refs, q_rows = _listed(refs, len(maps)), _listed(q_rows, len(maps))
+    maps = listed(maps)
+    refs, q_rows = listed(refs, len(maps)), listed(q_rows, len(maps))
     assert len(refs) == len(maps) == len(q_rows), (len(maps), len(refs), len(q_rows))
     parts = []
     if images is not None:
@@ -154,12 +147,7 @@ def q_rows_of_net(network) -> Dict[int, np.ndarray]:
 
 def rows_of(plan, image_chw) -> List[dict]:
     """What tf2_fid_describe reports, from the plan alone (n_doubled is the packed image's business: None here)"""
-    c, h, w = (int(v) for v in image_chw)
-    rows, rec = [dict(layer=-1, C=c, H=h, W=w, offset=0, n_doubled=0)], c
-    for L in plan:
-        rows.append(dict(layer=L.index, C=L.N, H=1 if L.endpool else L.PH, W=1 if L.endpool else L.PW, offset=rec * SLOTS * 8, n_doubled=None))
-        rec += L.N
-    return rows
+    return described_rows(plan, image_chw, SLOTS)
 
 
 def float_refs(tables, model, images, device=None, bn_eps: float = 1e-5) -> list:
@@ -262,34 +250,9 @@ def report(summ: Dict[int, dict], top: int = 10, layers: Optional[Dict[int, dict
 
 
 # ---- the device -------------------------------------------------------------------------------------------------------------------
-class FidelityHandle:
+class FidelityHandle(Handle):
     """tf2_fid_create on a packed NetWork with its Q table (no device needed): rows(), scales(), store_size"""
-
-    def __init__(self, network):
-        import ctypes as C
-        from . import _lib
-        self.net = network
-        h = C.c_void_p()
-        _lib.check(_lib.lib().tf2_fid_create(network._h, C.byref(h)))
-        self._h = h
-        self.store_size = int(_lib.lib().tf2_fid_store_size(h))
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            from . import _lib
-            _lib.lib().tf2_fid_destroy(h)
-            self._h = None
-
-    def rows(self) -> List[dict]:
-        """[{layer, C, H, W, offset (bytes), n_doubled}], row -1 first (tf2_fid_describe)"""
-        import ctypes as C
-        from . import _lib
-        cap = self.net.num_layer + 1
-        arr = (_lib.AuditRow * cap)()
-        n = C.c_int(0)
-        _lib.check(_lib.lib().tf2_fid_describe(self._h, arr, cap, C.byref(n)))
-        return [dict(layer=r.layer, C=r.C, H=r.H, W=r.W, offset=int(r.store_offset), n_doubled=r.n_doubled) for r in arr[:n.value]]
+    PREFIX, SLOTS = "fid", SLOTS
 
     def scales(self) -> np.ndarray:
         """[records] float32: 2^(Q + 8) of every record (tf2_fid_scales), the table the kernels read"""
@@ -303,7 +266,7 @@ class FidelityHandle:
         return out
 
 
-class DeviceComparator(FidelityHandle):
+class DeviceComparator(DeviceObserver, FidelityHandle):
     """The comparison of `network` (a NetWork, packed and bound) at one batch size: owns the handle, the keep_all workspace, the logits,
     the scale table and the int64 store as torch tensors.
       observe(images, refs)   one keep_all step and the comparison of every row behind it, enqueued on the current stream with no
@@ -320,59 +283,22 @@ class DeviceComparator(FidelityHandle):
 
     def __init__(self, network, batch: int, store=None):
         import torch
-        from . import _lib
-        super().__init__(network)
-        self.batch = int(batch)
-        dev = network.device
-        ws = int(_lib.lib().tf2_fid_workspace_size(self._h, self.batch))
-        self._ws = torch.empty(max(ws, 256), dtype=torch.uint8, device=dev)
-        nbytes = int(_lib.lib().tf2_net_logits_size(network._h, self.batch))
-        n_out = network.plan[-1].N
-        self._logits = torch.empty((self.batch, n_out) if nbytes == self.batch * n_out else (self.batch, nbytes // (self.batch * n_out), n_out),
-                                   dtype=torch.int8, device=dev)
-        self._scales = torch.from_numpy(self.scales()).to(dev)
+        super().__init__(network, batch, store)
+        self._scales = torch.from_numpy(self.scales()).to(network.device)
         self._rows = self.rows()
-        if store is None:
-            self.store_dev = torch.empty(self.store_size // 8, dtype=torch.int64, device=dev)
-            self.reset()
-        else:
-            assert store.dtype == torch.int64 and store.numel() * 8 >= self.store_size and store.device == dev
-            self.store_dev = store
-
-    def reset(self) -> None:
-        import torch
-        from . import _lib
-        stream = torch.cuda.current_stream(self.net.device).cuda_stream
-        _lib.check(_lib.lib().tf2_fid_store_init(self._h, self.store_dev.data_ptr(), self.store_dev.numel() * 8, stream))
 
     def _ref_array(self, refs):
         """the host array of device pointers tf2_fid_run reads at enqueue; every tensor checked against its row"""
-        import ctypes as C
-        import torch
-        nl = self.net.num_layer
-        refs = _listed(refs, nl) if isinstance(refs, dict) else list(refs)
-        assert len(refs) == nl, (len(refs), nl)
-        arr = (C.c_void_p * nl)()
-        for l, t in enumerate(refs):
-            if t is None:
-                arr[l] = None
-                continue
-            r = self._rows[l + 1]
-            assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.net.device, (l, t.dtype, t.device)
-            assert t.numel() == self.batch * r["C"] * r["H"] * r["W"] and t.shape[0] == self.batch and t.shape[1] == r["C"], (l, tuple(t.shape), r)
-            arr[l] = t.data_ptr()
-        return arr
+        return checked_refs(self._rows[1:], refs, self.batch, self.net.device)
 
     def _call(self, images, refs, kept: bool):
         import torch
         from . import _lib
-        assert images.is_contiguous() and images.device == self.net.device and images.dtype in (torch.float32, torch.int8)
-        assert images.shape[0] == self.batch, (images.shape, self.batch)
+        self._check_images(images)
         arr = self._ref_array(refs)
-        stream = torch.cuda.current_stream(self.net.device).cuda_stream
         L = _lib.lib()
         head = (self._h, images.data_ptr(), int(images.dtype == torch.int8), self.batch, self._ws.data_ptr(), self._ws.numel())
-        tail = (arr, self._scales.data_ptr(), self.store_dev.data_ptr(), self.store_dev.numel() * 8, stream)
+        tail = (arr, self._scales.data_ptr(), self.store_dev.data_ptr(), self.store_dev.numel() * 8, self._stream())
         _lib.check(L.tf2_fid_kept(*head, *tail) if kept else L.tf2_fid_run(*head, self._logits.data_ptr(), *tail))
 
     def observe(self, images, refs):
@@ -386,22 +312,5 @@ class DeviceComparator(FidelityHandle):
 
     def capture(self, images, refs, kept_only: bool = False):
         """kept_only: capture compare_kept(images, refs) instead of observe(images, refs)"""
-        import torch
-        dev = self.net.device
         step = (lambda: self.compare_kept(images, refs)) if kept_only else (lambda: self.observe(images, refs))
-        keep = self.store_dev.clone()
-        self.observe(images, refs)                  # warm-up outside the capture; the store is put back
-        self.store_dev.copy_(keep)
-        torch.cuda.synchronize(dev)
-        g = torch.cuda.CUDAGraph()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            with torch.cuda.graph(g, stream=side):
-                step()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        self._graph = g
-        return g.replay
-
-    def store(self) -> np.ndarray:
-        return self.store_dev.cpu().numpy()[:self.store_size // 8].reshape(-1, SLOTS).copy()
+        return self._capture(step, lambda: self.observe(images, refs))  # warm-up outside the capture; the store is put back

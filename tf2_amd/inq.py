@@ -244,19 +244,10 @@ class DeviceQuantizer:
     def capture(self, stream_dev, mask_dev, prev: float, cur: float, exp_floor: int = -127, codes=None, n_values: int = N_VALUES):
         """A HIP graph of step(...) on these buffers.  The warm-up call outside the capture is a real step: it changes stream_dev and
         mask_dev, so fill them before every replay."""
-        import torch
-        dev = stream_dev.device
-        self.step(stream_dev, mask_dev, prev, cur, exp_floor, codes, n_values)          # warm-up: buffers allocated, kernels loaded
-        torch.cuda.synchronize(dev)
-        g = torch.cuda.CUDAGraph()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            with torch.cuda.graph(g, stream=side):
-                self.step(stream_dev, mask_dev, prev, cur, exp_floor, codes, n_values)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        self._graph = g
-        return g.replay
+        from ._observe import capture_graph
+        # (the warm-up: buffers allocated, kernels loaded)
+        self._graph = capture_graph(lambda: self.step(stream_dev, mask_dev, prev, cur, exp_floor, codes, n_values), stream_dev.device)
+        return self._graph.replay
 
     def state(self) -> np.ndarray:
         assert self.state_dev is not None, "no step yet"

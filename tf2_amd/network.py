@@ -312,20 +312,10 @@ class Runner:
         it in place, call the returned function, read `self._logits`.
         concurrency as in run_batch -- state it: the capture runs on a side stream, so the library's stream history (-1) takes
         the step for one of several batches in flight and picks that launch plan (no group launches)."""
-        import torch
-        net = self.network
+        from ._observe import capture_graph
         step = (lambda: self.run_split(images, split)) if split > 1 else (lambda: self.run_batch(images, concurrency=concurrency))
-        step()                                      # warm-up: lazy attribute setup must not be captured
-        torch.cuda.synchronize(net.device)
-        g = torch.cuda.CUDAGraph()
-        side = torch.cuda.Stream(device=net.device)
-        side.wait_stream(torch.cuda.current_stream(net.device))
-        with torch.cuda.stream(side):
-            with torch.cuda.graph(g, stream=side):
-                step()
-        torch.cuda.current_stream(net.device).wait_stream(side)
-        self._graph = g
-        return g.replay
+        self._graph = capture_graph(step, self.network.device)      # (its warm-up: lazy attribute setup must not be captured)
+        return self._graph.replay
 
     def read_layer(self, layer: int, batch: int) -> np.ndarray:
         """Output of ``layer`` after a keep_all run, as NCHW int8 (per-layer parity tests)."""

@@ -32,6 +32,7 @@ def main():
     a = ap.parse_args()
     import torch
     from tf2_amd import audit as A, config as cfg, synth
+    from tf2_amd._observe import capture_graph
     from tf2_amd.network import NetWork, Runner
     assert torch.cuda.is_available(), "this tool measures on the GPU"
     dev = "cuda:0"
@@ -44,19 +45,7 @@ def main():
     aud = A.DeviceAuditor(net, B)
     runner = Runner(None, net)
 
-    def capture(step):
-        step()
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            with torch.cuda.graph(g, stream=side):
-                step()
-        torch.cuda.current_stream().wait_stream(side)
-        return g.replay
-
-    graphs = {"keep_all": capture(lambda: runner.run_batch(x, keep_all=True)),
+    graphs = {"keep_all": capture_graph(lambda: runner.run_batch(x, keep_all=True), dev).replay,
               "with_audit": aud.capture(x),
               "audit": aud.capture(x, kept_only=True)}
     s = torch.cuda.current_stream()
